@@ -13,12 +13,20 @@ handing off through tagged granules, csrc/smx_wplan.hpp; it also derives the piv
 column), and ONE sweep of the tableau (k_blk_sweep) applies all of them, so a sweep moves 16 B per
 element for P pivots (a chain of k pivots is cut into blocks of near-equal size: the driver's 20
 pivots are ONE sweep of 20, the sustained 200 nine of 22-23);
-bit-identical to one pivot per sweep.  After the timed region the
-line adds `sustained` (the next 200 pivots, HIP events around every sweep: the steady-state rate
-beside the burst) and times the one-pivot chain (k_update<kFused>, one kernel per pivot) as
-"single_pivot_update".
+bit-identical to one pivot per sweep.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and no more: it builds the LP, uploads it, runs
+the W warm-up pivots, times exactly K pivots, writes the outputs when --dump-outputs is given and
+prints the line (the roofline figures that come out of the timed region's own HIP events stay in
+it).  Everything that takes runs of its own sits behind --full: after the timed region the line
+then adds `parity` and `basis_cycle`, `sustained` (the next 200 pivots, HIP events around every
+sweep: the steady-state rate beside the burst), the copy ceiling, the one-pivot chain
+(k_update<kFused>, one kernel per pivot) as "single_pivot_update", and `cpu_baseline`; without
+--full those keys are null.  --dump-outputs DIR writes what the timed chain computed (pivot log,
+(x1, x2) history, the table's last column and f-row and a fixed seeded sample of its rows and
+columns) as DIR/<name>.npy, see dump_outputs.
 
 N = 1: one process.  N > 1: launched by torch.distributed.run, one rank per GPU; the tableau's
 constraint rows are block-partitioned (strong scaling of the same tableau) and run the
@@ -33,9 +41,9 @@ kernel's average duration measured with HIP events on the solver stream inside t
 (block chain: events around every sweep; graph paths: events around the replay / K, so
 inter-kernel gaps count as kernel time; N > 1: events around every update kernel).  traffic: HBM bytes per launch from
 the committed rocprofv3 PMC summary (profiles/), FETCH_SIZE doubled per the gfx950 correction.
-cpu_baseline: the numpy restatement of the same pivot (oracle/numpy_oracle.py, bit-identical to
-the reference) on the same tableau, single thread, a bounded number of pivots.
-parity: after the timed region the line checks itself against the C oracle's run of the same LP
+cpu_baseline (--full): the numpy restatement of the same pivot (oracle/numpy_oracle.py,
+bit-identical to the reference) on the same tableau, single thread, a bounded number of pivots.
+parity (--full): after the timed region the line checks itself against the C oracle's run of the same LP
 (tests/golden/bench16k.json, made in the build container by tests/golden/make_bench16k.py): every
 pivot (r, c) so far, and the SHA-256 of the whole table when the line stops at a pivot count the
 fixture hashes (25 = the driver's --warmup 5 --steps 20; 220 = the defaults).
@@ -86,7 +94,7 @@ def physical_check(name, bytes_per_launch, seconds_per_launch, footprint_bytes):
     return gbs
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -96,8 +104,10 @@ def parse():
     ap.add_argument("--cols", type=int, default=None, help="tableau columns C (default: --size)")
     ap.add_argument("--kind", default="uniform")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="--full: seconds of the numpy CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baselines")
     ap.add_argument("--traffic", default=None, help="PMC summary json (default: profiles/)")
     ap.add_argument("--sharded", action="store_true",
                     help="use the row-sharded RCCL path even at world size 1")
@@ -113,13 +123,22 @@ def parse():
                     help="N = 1: pivots per sweep (smx_tune_block; 0 = the library's policy, "
                          "20 at 16384^2)")
     ap.add_argument("--sustained", type=int, default=200,
-                    help="block path, N = 1: after the timed region, time this many further "
+                    help="--full, block path, N = 1: after the timed region, time this many further "
                          "pivots with HIP events around every sweep (the steady-state rate beside "
                          "the timed burst), then one more block after 1 s idle; 0 = off")
     ap.add_argument("--enqueue-probe", action="store_true",
                     help="row-sharded block path: after the timed region, time the host enqueue "
                          "per pivot of the eager and graph-captured chains (host_enqueue)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything beside the headline figure: "
+                         "parity against the C-oracle fixture, cycle detection, the sustained "
+                         "run, the copy ceiling, the one-pivot chain and the CPU baselines "
+                         "(a plain run sets up, warms up, times --steps pivots and prints)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed chain computed as "
+                         "DIR/<name>.npy (float64): the pivot log, the (x1, x2) history and a "
+                         "fixed seeded sample of the tableau (see dump_outputs)")
+    return ap.parse_args(argv)
 
 
 def load_traffic(path, workload):
@@ -387,6 +406,57 @@ def parity_check(dev, args, n, m, done):
             "sha256_equal": sha_ok, "fixture": "tests/golden/bench16k.json (C oracle)"}
 
 
+DUMP_LINES = 160     # sampled rows and sampled columns of a table too large to dump whole
+DUMP_WHOLE_BYTES = 32 << 20
+DUMP_PART_BYTES = 24 << 20
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dev, out_dir, done, suffix="", xhist=True):
+    """--dump-outputs: what the timed chain left for its caller after its last pivot, as
+    float64 ``out_dir/<name><suffix>.npy`` (under 64 MB in all):
+
+      pivot_log        (done, 2)  every pivot (r, c) applied so far, warm-up included
+      xhist            (done, 2)  (x1, x2) after each of them (the update kernel's own record)
+      rhs_column       (rows+1,)  the table's last column (b, then the objective's value)
+      objective_row    (C,)       the f-row
+      tableau          the whole table when it is at most 32 MiB, else
+      tableau_rows     (<=160, C) / tableau_row_index:    rows drawn once from a fixed seed
+      tableau_cols     (rows+1, <=160) / tableau_col_index: columns drawn from the same seed
+
+    The LP is seeded and the sample depends only on the table's shape, so two builds run with
+    the same arguments write arrays that compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    R, C = dev.rows + 1, dev.C
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"),
+                np.ascontiguousarray(arr, dtype=np.float64))
+
+    save("pivot_log", dev.read_log(0, done))
+    if xhist:
+        save("xhist", dev.read_xhist(0, done))
+    with torch.cuda.stream(dev.stream):
+        cur = dev.cur()
+        save("rhs_column", cur[:, C - 1].cpu().numpy())
+        save("objective_row", cur[R - 1, :C].cpu().numpy())
+        if 8 * R * C <= DUMP_WHOLE_BYTES:
+            save("tableau", cur[:, :C].cpu().numpy())
+            return
+        rng = np.random.default_rng(DUMP_SEED)
+        # at most DUMP_PART_BYTES per sample (a 65536 x 32768 table: 96 rows, 48 columns)
+        nr = max(1, min(DUMP_LINES, R, DUMP_PART_BYTES // (8 * C)))
+        nc = max(1, min(DUMP_LINES, C, DUMP_PART_BYTES // (8 * R)))
+        ri = np.sort(rng.choice(R, size=nr, replace=False))
+        ci = np.sort(rng.choice(C, size=nc, replace=False))
+        save("tableau_row_index", ri)
+        save("tableau_col_index", ci)
+        save("tableau_rows", cur[torch.from_numpy(ri).to(cur.device), :C].cpu().numpy())
+        save("tableau_cols", cur[:, torch.from_numpy(ci).to(cur.device)].cpu().numpy())
+
+
 def run_single(args):
     import numpy as np
     import torch
@@ -484,8 +554,11 @@ def run_single(args):
     ctl = dev.sync_state()
     done = int(ctl["npivots"])
     valid = done == args.warmup + args.steps and not ctl["term"]
-    cycle = cycle_report(n, m, dev.read_log(0, done))
-    parity = parity_check(dev, args, n, m, done)
+    if args.dump_outputs:
+        dump_outputs(dev, args.dump_outputs, done)
+    full = args.full
+    cycle = cycle_report(n, m, dev.read_log(0, done)) if full else None
+    parity = parity_check(dev, args, n, m, done) if full else None
     if resident is not None:
         # algorithmic bytes of a chain held in LDS: not an HBM rate, no physical bound applies
         achieved = bytes_per_sweep / avg_kernel / 1e9
@@ -496,11 +569,12 @@ def run_single(args):
         achieved = physical_check(kernel, bytes_per_sweep, avg_kernel, 8.0 * R * C)
     workload =f"{R}x{C} dense fp64 tableau, {args.kind} random LP seed {args.seed}"
     sustained = None
-    if bplan is not None and valid and args.sustained > 0:
+    if full and bplan is not None and valid and args.sustained > 0:
         sustained = sustained_record(dev, bplan[1], args.sustained)
-    copy_gbs = copy_ceiling(8.0 * R * C)   # same bytes as one sweep (outside timing)
+    # same bytes as one sweep (outside timing)
+    copy_gbs = copy_ceiling(8.0 * R * C) if full else None
     single = None
-    if bplan is not None and valid:
+    if full and bplan is not None and valid:
         single = _single_pivot_line(dev, R, C, 20)
     out = {
         "metric": METRIC,
@@ -514,6 +588,7 @@ def run_single(args):
         "scaling": "strong",
         "vs_baseline": None,
         "dtype": "f64",
+        "full": bool(full),
         "data": "synthetic: seeded dense random LP generated on the host, uploaded to HBM "
                 "before timing (no dataset)",
         "config": {"workload": workload, "rows": R, "cols": C, "n": n, "m": m,
@@ -532,14 +607,15 @@ def run_single(args):
                           "unit": "GB/s", "frac": achieved / PEAK_HBM_GBS, "traffic": traffic,
                           "kernel": kernel, "algorithmic_bytes_per_launch": bytes_per_sweep,
                           "avg_kernel_ms": avg_kernel * 1e3,
-                          "copy_ceiling_gbs": copy_gbs, "frac_of_copy": achieved / copy_gbs},
+                          "copy_ceiling_gbs": copy_gbs,
+                          "frac_of_copy": None if copy_gbs is None else achieved / copy_gbs},
                          **extra),
         "single_pivot_update": single,
         "sustained": sustained,
         "trajectory_valid": bool(valid),
         "basis_cycle": cycle,
     }
-    if not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(T, n, m, args.cpu_seconds)
     else:
         out["cpu_baseline"] = None
@@ -571,7 +647,14 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 or args.gpus > 1 or args.sharded:
         from simplex_mi355x import sharded
-        sharded.bench_main(args, METRIC, PEAK_HBM_GBS, cpu_baseline, load_traffic)
+        dump = None
+        if args.dump_outputs:
+            def dump(dev, done, rank, world):
+                # every rank writes its own row block (plus the f-row it carries)
+                dump_outputs(dev, args.dump_outputs, done,
+                             suffix=f"_rank{rank}" if world > 1 else "", xhist=False)
+        sharded.bench_main(args, METRIC, PEAK_HBM_GBS, cpu_baseline if args.full else None,
+                           load_traffic, after_timed=dump)
     else:
         run_single(args)
 

@@ -555,7 +555,11 @@ def sharded_cpu_baseline(cpu_baseline_fn, args, n: int, m: int, lo: int, hi: int
     return out
 
 
-def bench_main(args, metric, peak_gbs, cpu_baseline_fn=None, load_traffic=None):
+def bench_main(args, metric, peak_gbs, cpu_baseline_fn=None, load_traffic=None,
+               after_timed=None):
+    """``after_timed(dev, npivots, rank, world)``, when given, runs on every rank right after the
+    timed region, on the rank's DeviceTableau as the timed chain left it (bench.py
+    --dump-outputs)."""
     for k, v in (("MASTER_ADDR", "127.0.0.1"), ("MASTER_PORT", "29511"), ("RANK", "0"),
                  ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")):
         os.environ.setdefault(k, v)   # plain `python bench.py --sharded` = a 1-rank job
@@ -606,6 +610,8 @@ def bench_main(args, metric, peak_gbs, cpu_baseline_fn=None, load_traffic=None):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     st = be.state()
+    if after_timed is not None:
+        after_timed(be.dev, st["npivots"], rank, world)
     cycle = None
     if rank == 0:
         from .basis import BasisTracker

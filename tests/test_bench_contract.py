@@ -148,6 +148,22 @@ def _bench_module():
     return bench
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    """--full (everything beside the headline figure) is off by default; --dump-outputs takes a
+    directory; the dump's seeded sample stays under 64 MB for the largest configured table."""
+    bench = _bench_module()
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 20 and a.warmup == 5
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    # a small table is written whole, a larger one as two samples: either way under the budget
+    assert bench.DUMP_WHOLE_BYTES + 32 * (1 << 16) < 64 * 10**6
+    for R, C in ((16384, 16384), (65536, 32768)):
+        part = 8 * R * min(bench.DUMP_LINES, bench.DUMP_PART_BYTES // (8 * R)) \
+            + 8 * C * min(bench.DUMP_LINES, bench.DUMP_PART_BYTES // (8 * C))
+        assert part + 8 * (R + C) + 32 * (1 << 16) < 64 * 10**6
+
+
 def test_physical_guard_rejects_impossible_rates():
     """bench.physical_check refuses a launch that would move bytes faster than the memory system
     can (the round-3 forced-update record: 1.07 GB in 0.26 us); accepts the real ones."""

@@ -253,6 +253,48 @@ def test_bench_single_and_sharded_paths():
         assert rec["roofline"]["bound"] == "hbm" and 0 < rec["roofline"]["frac"] < 1
 
 
+def test_bench_plain_run_dumps_the_timed_chains_outputs(tmp_path):
+    """A plain run (no --full) of a block-pivot table (3072^2, 72 MiB: sampled dump) times exactly
+    --steps pivots, leaves everything that needs runs of its own out of the line, and
+    --dump-outputs writes what the chain computed: the pivot log and the sampled rows / columns,
+    the last column and the f-row equal the C oracle's after warmup + steps pivots bit for bit."""
+    import bench
+    from oracle import c_oracle
+    from simplex_mi355x import lp
+    n = m = 3071
+    warm, steps = 3, 13
+    rec = _bench_json(["bench.py", "--size", str(n + 1), "--steps", str(steps), "--warmup",
+                       str(warm), "--dump-outputs", str(tmp_path)])
+    assert rec["steps"] == steps and rec["warmup"] == warm and rec["trajectory_valid"]
+    assert rec["full"] is False and rec["unit"] == "pivots/s" and rec["dtype"] == "f64"
+    assert rec["value"] == pytest.approx(1e3 / rec["ms_per_step"], rel=1e-6)
+    assert rec["roofline"]["kernel"].startswith("k_blk_sweep<")
+    for k in ("cpu_baseline", "sustained", "single_pivot_update", "parity", "basis_cycle"):
+        assert rec[k] is None, k
+    assert rec["roofline"]["copy_ceiling_gbs"] is None
+    got = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert set(got) == {"pivot_log", "xhist", "rhs_column", "objective_row", "tableau_rows",
+                        "tableau_row_index", "tableau_cols", "tableau_col_index"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 * 10**6
+    T = lp.dense_tableau("uniform", 0, n, m)
+    Tref, st, done, log = c_oracle.run(T, n, m, m, warm + steps, threads=8)
+    assert done == warm + steps
+    assert np.array_equal(got["pivot_log"], np.asarray(log, dtype=np.float64))
+    assert got["xhist"].shape == (done, 2)
+    ri = got["tableau_row_index"].astype(np.int64)
+    ci = got["tableau_col_index"].astype(np.int64)
+    assert len(ri) == len(ci) == bench.DUMP_LINES and ri.max() <= n and ci.max() <= m
+    # the oracle's f-row is not the device's running f-row layout: constraint rows only
+    rows = ri[ri < n]
+    assert np.array_equal(got["tableau_rows"][ri < n].view(np.int64), Tref[rows].view(np.int64))
+    assert np.array_equal(got["tableau_cols"][:n].view(np.int64),
+                          np.ascontiguousarray(Tref[:n][:, ci]).view(np.int64))
+    assert np.array_equal(got["rhs_column"][:n].view(np.int64), Tref[:n, m].view(np.int64))
+    assert got["objective_row"].shape == (m + 1,)
+    assert np.array_equal(got["objective_row"][ci], got["tableau_cols"][n])
+
+
 # ----------------------------------------------------------------------------------------------
 # 8. device-resident history: lazy get_solution == eager get_solution, tables bit-identical
 def _same_infos(a, b):

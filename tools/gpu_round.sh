@@ -8,7 +8,7 @@
 #   pytest                 the full `pytest -m gpu` suite (the driver's round-end tier)
 #   pytest=FILES           those test files (comma separated) with -m gpu
 #   smoke                  __graft_entry__.smoke()
-#   bench20 / bench200     bench.py --steps 20 --warmup 5 (the driver's line) / --steps 200 --warmup 20
+#   bench20 / bench200     bench.py --full --steps 20 --warmup 5 (the whole line) / --steps 200 --warmup 20
 #   benchN=ARGS            bench.py with ARGS (`benchN=--size,8192,--steps,200` -> benchN.log)
 #   stats20 / stats200     rocprofv3 --kernel-trace --stats of bench20 / bench200 (no cpu baseline)
 #   statsN=ARGS            rocprofv3 --kernel-trace --stats of bench.py ARGS (-> gpurun_out/TAG/N_statsN/)
@@ -37,7 +37,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 export TMPDIR=/tmp
 export STEPS_LOGDIR=$O
-B="python3 $R/bench.py --no-cpu-baseline"
+B="python3 $R/bench.py --full --no-cpu-baseline"
 STEPS=()
 n=0
 for spec in "$@"; do
@@ -57,8 +57,8 @@ for spec in "$@"; do
       cmd="cd $R && python -u -m pytest $files -m gpu -x -q --timeout 300 --timeout-method thread"
       d=900 ;;
     smoke) cmd="cd $R && python -u -c 'import __graft_entry__ as g; g.smoke()'"; d=180 ;;
-    bench20) cmd="cd $R && python -u bench.py --gpus 1 --steps 20 --warmup 5"; d=300 ;;
-    bench200) cmd="cd $R && python -u bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline"; d=300 ;;
+    bench20) cmd="cd $R && python -u bench.py --gpus 1 --steps 20 --warmup 5 --full"; d=300 ;;
+    bench200) cmd="cd $R && python -u bench.py --gpus 1 --steps 200 --warmup 20 --full --no-cpu-baseline"; d=300 ;;
     benchN) cmd="cd $R && python -u bench.py $arg"; d=400 ;;
     stats20) cmd="cd /tmp && rocprofv3 --kernel-trace --stats -d $O/stats20 -o run --output-format csv -- $B --steps 20 --warmup 5"; d=300 ;;
     statsN) cmd="cd /tmp && rocprofv3 --kernel-trace --stats -d $O/$tag -o run --output-format csv -- $B $arg"; d=300 ;;

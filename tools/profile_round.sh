@@ -13,7 +13,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 export TMPDIR=/tmp
 export STEPS_LOGDIR=$ROOT/gpurun_out
 mkdir -p "$OUT"
-B="python3 $ROOT/bench.py --no-cpu-baseline"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline"
 cd /tmp || exit 1
 "$ROOT/tools/gpu_steps.sh" \
   "stats16k|300|rocprofv3 --kernel-trace --stats -d $OUT/stats16k -o run --output-format csv -- $B --steps 100 --warmup 10 > $OUT/bench16k.log 2>&1" \
