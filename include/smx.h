@@ -184,6 +184,20 @@ int smx_batch_solve(const double* tabs, const int32_t* dims, int32_t B, int32_t 
                     int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
                     double* snaps, int32_t* status, int32_t* npivots, void* stream);
 
+/* ---- batched mid-sized LPs (one workgroup per LP, tableau in LDS) -------------------------
+ * The same call as smx_batch_solve -- every layout and meaning identical -- for problems past one
+ * wavefront: Rmax >= 2 rows and ldb >= 2 columns, as large as one CU's LDS holds
+ * (smx_batch_wg_lds_bytes(Rmax, ldb) >= 0; about 141 x 141, 301 x 41 or 41 x 301).  Every problem
+ * must have 1 <= n_b < Rmax and 1 <= m_b < ldb; one that does not is left with status SMX_IDLE
+ * and no pivots.  Returns hipErrorInvalidValue (1) before any HIP call for B < 0, Rmax < 2,
+ * ldb < 2, max_pivots < 0 or a shape that does not fit; B == 0 returns 0 without a launch. */
+int smx_batch_solve_wg(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                       int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                       double* snaps, int32_t* status, int32_t* npivots, void* stream);
+/* Host only: the dynamic LDS (bytes) one workgroup of smx_batch_solve_wg needs for a launch of
+ * Rmax x ldb blocks, or -1 when the shape is outside its envelope. */
+int64_t smx_batch_wg_lds_bytes(int32_t Rmax, int32_t ldb);
+
 /* ---- row-sharded engine (one process per GPU; exchange = caller's all-gather) ----------
  * Local tableau: shape->rows constraint rows (global rows row0 .. row0+rows-1) + a replica
  * of the f-row as local row `rows`.  Per pivot:

@@ -8,6 +8,7 @@
 //   smx_update.hpp    k_update: recalculate_matrix (simplex.py:143-177), every mode
 //   smx_shard.hpp     row-sharded exchange kernels
 //   smx_batch.hpp     k_copy (copy-ceiling probe), k_batch (one small LP per wavefront)
+//   smx_batch_wg.hpp  k_batch_wg (one mid-sized LP per workgroup, tableau in LDS)
 //   smx_resident.hpp  k_resident: the whole pivot loop in one persistent launch, tableau in LDS
 //   smx_block.hpp     k_blk_*: P pivots per HBM sweep, decisions planned from the sweep's input
 // and this file holds the host side: grid sizing, variants, chains, graphs, RCCL, the C ABI.
@@ -51,6 +52,7 @@ static_assert(sizeof(smx_part) == 32, "smx_part layout");
 #include "smx_update.hpp"
 #include "smx_shard.hpp"
 #include "smx_batch.hpp"
+#include "smx_batch_wg.hpp"
 #include "smx_resident.hpp"
 #include "smx_block.hpp"
 #include "smx_window.hpp"
@@ -1129,6 +1131,57 @@ int smx_batch_solve(const double* tabs, const int32_t* dims, int32_t B, int32_t 
     else
         hipLaunchKernelGGL(k_batch<64>, grid, block, 0, st, tabs, dims, B, Rmax, ldb, max_pivots,
                            out, rc, xv, snaps, status, npivots);
+    return (int)hipGetLastError();
+}
+
+// ---- batched mid-sized LPs (smx_batch_wg.hpp) ------------------------------------------------
+// The envelope: the table at an odd row pitch, the old pivot row and the old pivot column in
+// dynamic LDS, within a CU's 160 KiB less the kernel's static part (the reduction partials,
+// under 1 KiB) -- the kResLdsMax precedent.
+namespace {
+
+constexpr int64_t kWgLdsMax = 160 * 1024 - 1024;
+
+inline int64_t wg_ldl(int64_t ldb) { return ldb | 1; }
+
+inline int64_t wg_lds_bytes(int64_t Rmax, int64_t ldb) {
+    if (Rmax < 2 || ldb < 2 || Rmax > kWgLdsMax || ldb > kWgLdsMax) return -1;
+    const int64_t bytes = (Rmax * wg_ldl(ldb) + ldb + Rmax) * 8;
+    return bytes <= kWgLdsMax ? bytes : -1;
+}
+
+// Workgroup size: about 16 table elements per thread -- the largest power of two of threads
+// that leaves each at least 16 of the launch's Rmax x ldb elements, within 256..1024.  Measured
+// (DESIGN 9.1): 2048 LPs of 100 x 100 take 20.2 / 15.3 / 17.7 ms at 256 / 512 / 1024 threads,
+// of 65 x 65 4.75 / 6.66 / 14.3 ms.  Fewer elements per thread and the four barriers and two
+// merges of a step outweigh the shorter update; more and the divisions queue up behind one wave.
+inline int wg_block(int64_t Rmax, int64_t ldb) {
+    int t = kWgMaxBlock;
+    while (t > 256 && (int64_t)t * 16 > Rmax * ldb) t /= 2;
+    return t;
+}
+
+}  // namespace
+
+int64_t smx_batch_wg_lds_bytes(int32_t Rmax, int32_t ldb) { return wg_lds_bytes(Rmax, ldb); }
+
+int smx_batch_solve_wg(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                       int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                       double* snaps, int32_t* status, int32_t* npivots, void* stream) {
+    if (B < 0 || Rmax < 2 || ldb < 2 || max_pivots < 0) return (int)hipErrorInvalidValue;
+    const int64_t lds = wg_lds_bytes(Rmax, ldb);
+    if (lds < 0) return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    static std::once_flag once;
+    static hipError_t attr_err = hipSuccess;
+    std::call_once(once, [] {
+        attr_err = hipFuncSetAttribute((const void*)k_batch_wg,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgLdsMax);
+    });
+    if (attr_err != hipSuccess) return (int)attr_err;
+    hipLaunchKernelGGL(k_batch_wg, dim3(B), dim3(wg_block(Rmax, ldb)), (size_t)lds, S(stream),
+                       tabs, dims, B, Rmax, ldb, (int)wg_ldl(ldb), max_pivots, out, rc, xv, snaps,
+                       status, npivots);
     return (int)hipGetLastError();
 }
 

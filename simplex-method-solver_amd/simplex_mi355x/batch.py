@@ -6,9 +6,11 @@ GPU one such solve is pure launch latency.  ``solve_batch`` packs up to millions
 wavefront of ``k_batch`` (csrc/smx_batch.hpp).  Per problem the result is exactly what
 ``SimplexMethod(constraints, function).get_solution()`` returns (simplex.py:179-199): the list of
 ``Info`` snapshots (labels, table, i/j, x1/x2/optimum) with the trailing ``Error`` on the two
-``ValueError`` outcomes.  Problems outside the batch kernel's envelope (bigger, ragged, or with a
-``len(function)`` the reference would index out of range) go through ``SimplexMethod`` one by one
--- still on the device.
+``ValueError`` outcomes.  Problems past that envelope whose table still fits one CU's LDS (to
+about 140 x 140, 300 x 40 or 40 x 300) run one workgroup each in ``k_batch_wg``
+(csrc/smx_batch_wg.hpp), grouped into launches of similar size (``wg_launches``).  Problems
+outside both envelopes (bigger, ragged, int entries, or with a ``len(function)`` the reference
+would index out of range) go through ``SimplexMethod`` one by one -- still on the device.
 """
 from __future__ import annotations
 
@@ -20,23 +22,78 @@ import torch
 from . import _lib
 from .engine import MESSAGES, Error, Info, SimplexMethod
 
+# The wave kernel's envelope (k_batch): past it a launch goes to the workgroup kernel
+# (k_batch_wg), whose own envelope -- what one CU's LDS holds -- only the library states
+# (smx_batch_wg_lds_bytes).
 MAX_ROWS = 64      # one wavefront: rows 0..n (f-row = lane n)
 MAX_COLS = 64      # register-resident row of at most 64 doubles
+
+KERNELS = ("auto", "wave", "workgroup")
+ENVELOPE_ERROR = "a problem is outside the batch kernel's envelope"
+# history=True: one workgroup launch's snapshot buffer ([B][max_pivots][Rmax][ldb] doubles; a
+# 128 x 128 LP with max_pivots=256 is 32 MiB) stays under this many bytes -- a bucket is split
+# into as many launches as that takes (a single LP is never split).
+SNAP_BUDGET = 1 << 30
+
+
+def wg_lds_bytes(Rmax: int, ldb: int) -> int:
+    """Dynamic LDS one workgroup of k_batch_wg needs for a launch of Rmax x ldb blocks, -1 when
+    the shape is outside that kernel's envelope (the library is the one source of the rule)."""
+    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
+        return -1
+    return int(_lib.load().smx_batch_wg_lds_bytes(int(Rmax), int(ldb)))
+
+
+def _shape(cons, func):
+    """(n, m, flen) of a problem the batch kernels can take if it holds floats only (rectangular,
+    a ``len(function)`` the reference does not index out of range), else None."""
+    if not cons:
+        return None
+    m = len(cons[0]) - 1
+    n = len(cons)
+    if m < 1 or any(len(r) != m + 1 for r in cons):
+        return None
+    flen = len(func)
+    if flen not in (m, m + 1) or flen < 2:
+        return None
+    return n, m, flen
 
 
 def _eligible(cons, func) -> bool:
     if not cons:
         return False
-    m = len(cons[0]) - 1
-    n = len(cons)
-    if n + 1 > MAX_ROWS or m + 1 > MAX_COLS or m < 1:
+    if len(cons) + 1 > MAX_ROWS or len(cons[0]) > MAX_COLS:
         return False
-    if any(len(r) != m + 1 for r in cons):
-        return False
-    flen = len(func)
     # int entries: the reference's first pivot runs in int arithmetic, whose zero signs differ
-    # from fp64's (engine._int_entries); SimplexMethod applies that fix, k_batch does not
-    return flen in (m, m + 1) and flen >= 2 and not _has_ints(cons, func)
+    # from fp64's (engine._int_entries); SimplexMethod applies that fix, the batch kernels do not
+    return _shape(cons, func) is not None and not _has_ints(cons, func)
+
+
+def route(constraints, function) -> str:
+    """Where ``solve_batch`` sends a problem: ``"wave"`` (k_batch, one wavefront per LP),
+    ``"workgroup"`` (k_batch_wg, one workgroup per LP, tableau in LDS) or ``"single"``
+    (``SimplexMethod``, one by one: int entries, ragged rows, tables past one CU's LDS and the
+    reference's IndexError cases).  Host only."""
+    if _eligible(constraints, function):
+        return "wave"
+    shp = _shape(constraints, function)
+    if (shp is not None and wg_lds_bytes(shp[0] + 1, shp[1] + 1) >= 0
+            and not _has_ints(constraints, function)):
+        return "workgroup"
+    return "single"
+
+
+def choose_kernel(Rmax: int, ldb: int, kernel: str = "auto") -> str:
+    """The kernel a launch of Rmax x ldb blocks runs on: ``"auto"`` takes the wave kernel inside
+    its envelope and the workgroup kernel past it; ``"wave"`` / ``"workgroup"`` force one.
+    Raises ValueError when the shape fits none of the kernels allowed."""
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    if kernel != "workgroup" and Rmax <= MAX_ROWS and ldb <= MAX_COLS:
+        return "wave"
+    if kernel != "wave" and wg_lds_bytes(Rmax, ldb) >= 0:
+        return "workgroup"
+    raise ValueError(ENVELOPE_ERROR)
 
 
 def _has_ints(cons, func) -> bool:
@@ -47,8 +104,9 @@ def _has_ints(cons, func) -> bool:
             if row.dtype.kind in "iub":
                 return True
             continue
-        for x in row:
-            if type(x) is not float and isinstance(x, (int, np.integer)):
+        # by the set of element types: a 100 x 100 LP is 10 000 entries and almost always all float
+        for t in set(map(type, row)):
+            if t is not float and issubclass(t, (int, np.integer)):
                 return True
     return False
 
@@ -70,12 +128,15 @@ def _fallback(cons, func, max_pivots, history):
 
 
 def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256,
-                       history: bool = False, device=None) -> dict:
+                       history: bool = False, device=None, kernel: str = "auto") -> dict:
     """Array-level batch solve (no Python objects per problem).
 
     ``tabs``: float64 [B][Rmax][ldb], problem k in rows 0..n_k (f-row = row n_k), columns
     0..m_k; ``dims``: int32 [B][3] = (n, m, len(function)) with every problem inside the kernel's
-    envelope (see ``eligible``).  Returns numpy arrays: ``final`` (same layout as tabs),
+    envelope (see ``route``).  ``kernel``: ``"auto"`` runs the launch on the wave kernel when
+    Rmax <= 64 and ldb <= 64 and on the workgroup kernel past that, up to what one CU's LDS
+    holds; ``"wave"`` / ``"workgroup"`` force one (``choose_kernel``).  A shape that fits none
+    raises ValueError.  Returns numpy arrays: ``final`` (same layout as tabs),
     ``status`` (SMX_* codes; SMX_PIVOT = max_pivots reached), ``npivots``, ``rc`` [B][P][2],
     ``xv`` [B][P][2] (x1, x2 after each pivot) and, with ``history``, ``snaps``
     [sum(npivots)][Rmax][ldb] -- problem k's tables after each of its pivots are
@@ -88,11 +149,14 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
     B, Rmax, ldb = tabs.shape
     if dims.shape != (B, 3):
         raise ValueError("dims must be int32 [B][3]")
-    if B and (Rmax > MAX_ROWS or ldb > MAX_COLS or (dims[:, 0] + 1 > Rmax).any() or
-              (dims[:, 1] + 1 > ldb).any() or (dims[:, 1] < 1).any() or (dims[:, 0] < 1).any()):
-        raise ValueError("a problem is outside the batch kernel's envelope")
+    which = choose_kernel(Rmax, ldb, kernel) if B else "wave"
+    if B and ((dims[:, 0] + 1 > Rmax).any() or (dims[:, 1] + 1 > ldb).any() or
+              (dims[:, 1] < 1).any() or (dims[:, 0] < 1).any()):
+        raise ValueError(ENVELOPE_ERROR)
     P = int(max_pivots)
     L = _lib.load()
+    solve, what = ((L.smx_batch_solve, "smx_batch_solve") if which == "wave" else
+                   (L.smx_batch_solve_wg, "smx_batch_solve_wg"))
     dev = torch.device(device if device is not None else "cuda")
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
@@ -105,10 +169,10 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
                    if history else None)
         d_st = torch.zeros(B, dtype=torch.int32, device=dev)
         d_np = torch.zeros(B, dtype=torch.int32, device=dev)
-        _lib.check(L.smx_batch_solve(
+        _lib.check(solve(
             d_tabs.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, P, d_out.data_ptr(),
             d_rc.data_ptr(), d_xv.data_ptr(), d_snaps.data_ptr() if history else None,
-            d_st.data_ptr(), d_np.data_ptr(), stream.cuda_stream), "smx_batch_solve")
+            d_st.data_ptr(), d_np.data_ptr(), stream.cuda_stream), what)
         res = {"final": d_out.cpu().numpy(), "rc": d_rc.cpu().numpy(),
                "xv": d_xv.cpu().numpy(), "status": d_st.cpu().numpy(),
                "npivots": d_np.cpu().numpy()}
@@ -135,41 +199,92 @@ def pack(problems):
     return tabs, dims
 
 
-def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=None):
+def wg_launches(shapes, max_pivots: int, history: bool):
+    """Split workgroup-kernel problems into launches; ``shapes[q]`` = (n, m) of problem q, the
+    result is a list of index lists.
+
+    A launch pads every member to its largest rows x columns, and that padded block is what each
+    workgroup holds in LDS, so one big member would cost all the others occupancy.  The rule: sort
+    by own LDS footprint (``wg_lds_bytes(n + 1, m + 1)``); a launch takes the next problem while
+    its padded footprint still fits the kernel and stays within twice the footprint of its
+    smallest (first) member.  With ``history`` a launch also ends where its snapshot buffer
+    would pass ``SNAP_BUDGET``."""
+    order = sorted(range(len(shapes)), key=lambda q: wg_lds_bytes(shapes[q][0] + 1,
+                                                                 shapes[q][1] + 1))
+    launches = []
+    cur, R, C, floor = [], 0, 0, 0
+    for q in order:
+        n, m = shapes[q]
+        R2, C2 = max(R, n + 1), max(C, m + 1)
+        lds = wg_lds_bytes(R2, C2)
+        snap = (len(cur) + 1) * max(int(max_pivots), 1) * R2 * C2 * 8 if history else 0
+        if cur and (lds < 0 or lds > 2 * floor or snap > SNAP_BUDGET):
+            launches.append(cur)
+            cur, R2, C2 = [], n + 1, m + 1
+        if not cur:
+            floor = wg_lds_bytes(R2, C2)
+        cur.append(q)
+        R, C = R2, C2
+    if cur:
+        launches.append(cur)
+    return launches
+
+
+def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=None,
+                kernel: str = "auto"):
     """Solve every ``(constraints, function)``; returns ``(results, statuses)``.
 
     ``results[k]`` is the ``get_solution()`` list of problem k (``history=False``: only the
     initial and the final ``Info``, like ``SimplexMethod.solve(record_history=False)``), or the
     ``IndexError`` the reference would raise.  ``statuses[k]`` is ``"optimum"``, ``"error"``,
-    ``"cap"`` (``max_pivots`` reached) or ``"exception"``."""
+    ``"cap"`` (``max_pivots`` reached) or ``"exception"``.
+
+    Each problem goes where ``route`` says: the wave problems in one launch, the workgroup
+    problems in the launches of ``wg_launches``, the rest through ``SimplexMethod`` one by one.
+    ``kernel="workgroup"`` sends the wave problems through the workgroup kernel too;
+    ``kernel="wave"`` raises ValueError if a problem needs the workgroup kernel."""
     problems = list(problems)
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
     if not torch.cuda.is_available():
         raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
     results = [None] * len(problems)
     statuses = [None] * len(problems)
-    idx = [k for k, (c, f) in enumerate(problems) if _eligible(c, f)]
-    batched = set(idx)
+    routes = [route(c, f) for c, f in problems]
+    if kernel == "wave" and "workgroup" in routes:
+        raise ValueError(ENVELOPE_ERROR)
+    if kernel == "workgroup":
+        routes = ["workgroup" if r == "wave" else r for r in routes]
     for k, (c, f) in enumerate(problems):
-        if k not in batched:
+        if routes[k] == "single":
             results[k], statuses[k] = _fallback(c, f, max_pivots, history)
-    if not idx:
-        return results, statuses
-    tabs, dims = pack([problems[k] for k in idx])
-    out = solve_batch_arrays(tabs, dims, max_pivots, history, device)
+    launches = []                                            # (kernel, problem indices)
+    idx = [k for k, r in enumerate(routes) if r == "wave"]
+    if idx:
+        launches.append(("wave", idx))
+    idx = [k for k, r in enumerate(routes) if r == "workgroup"]
+    if idx:
+        shapes = [(len(problems[k][0]), len(problems[k][0][0]) - 1) for k in idx]
+        launches += [("workgroup", [idx[q] for q in part])
+                     for part in wg_launches(shapes, max_pivots, history)]
     P = int(max_pivots)
-    # Hundreds of thousands of fresh, acyclic lists: pause the cyclic collector while they are
-    # built, or its generational passes rescan the growing result set (5x slower at 20k LPs).
-    gc_was_on = gc.isenabled()
-    gc.disable()
-    try:
-        for q, k in enumerate(idx):
-            results[k], statuses[k] = _assemble(
-                problems[k], dims[q], out["final"][q], out["rc"][q], out["xv"][q],
-                out["snaps"][out["snap_off"][q]:out["snap_off"][q + 1]] if history else None,
-                int(out["status"][q]), int(out["npivots"][q]), P)
-    finally:
-        if gc_was_on:
-            gc.enable()
+    for which, idx in launches:
+        tabs, dims = pack([problems[k] for k in idx])
+        out = solve_batch_arrays(tabs, dims, max_pivots, history, device, kernel=which)
+        # Hundreds of thousands of fresh, acyclic lists: pause the cyclic collector while they
+        # are built, or its generational passes rescan the growing result set (5x slower at 20k
+        # LPs).
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            for q, k in enumerate(idx):
+                results[k], statuses[k] = _assemble(
+                    problems[k], dims[q], out["final"][q], out["rc"][q], out["xv"][q],
+                    out["snaps"][out["snap_off"][q]:out["snap_off"][q + 1]] if history else None,
+                    int(out["status"][q]), int(out["npivots"][q]), P)
+        finally:
+            if gc_was_on:
+                gc.enable()
     return results, statuses
 
 
