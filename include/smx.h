@@ -198,6 +198,26 @@ int smx_batch_solve_wg(const double* tabs, const int32_t* dims, int32_t B, int32
  * Rmax x ldb blocks, or -1 when the shape is outside its envelope. */
 int64_t smx_batch_wg_lds_bytes(int32_t Rmax, int32_t ldb);
 
+/* ---- batched LPs past one CU's LDS (one workgroup per LP, tableau in global memory) -------
+ * The same call as smx_batch_solve_wg -- every layout, status and meaning identical -- with the
+ * working table in out[b] instead of LDS, so it runs at any shape from 2 x 2 up to the envelope
+ * smx_batch_gm_fits states: Rmax, ldb >= 2, Rmax + ldb <= 8192 and Rmax * ldb <= 2^19 (724 x
+ * 724; every shape smx_batch_solve_wg takes fits too).  out must not overlap tabs.  Returns
+ * hipErrorInvalidValue (1) before any HIP call for B < 0, Rmax < 2, ldb < 2, max_pivots < 0 or a
+ * shape outside the envelope; B == 0 returns 0 without a launch. */
+int smx_batch_solve_gm(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                       int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                       double* snaps, int32_t* status, int32_t* npivots, void* stream);
+/* Host only: 1 when a launch of Rmax x ldb blocks is inside smx_batch_solve_gm's envelope, else
+ * 0.  The single statement of that envelope. */
+int smx_batch_gm_fits(int32_t Rmax, int32_t ldb);
+/* Measurement knob (tools/bench_batch_gm.py) for later smx_batch_solve_gm calls: workgroup size
+ * (256, 512 or 1024), the LDS mirrors of the f-row and "-b" column (0 / 1) and how many table
+ * elements a thread loads ahead of its divisions in the update (1, 4 or 8); any other value
+ * keeps that setting.  Returns the previous block | mirrors << 16 | unroll << 20.  Results do not
+ * depend on any of them.  Defaults (the measured winners): 1024, 0, 8. */
+int smx_tune_batch_gm(int32_t block, int32_t mirrors, int32_t unroll);
+
 /* ---- row-sharded engine (one process per GPU; exchange = caller's all-gather) ----------
  * Local tableau: shape->rows constraint rows (global rows row0 .. row0+rows-1) + a replica
  * of the f-row as local row `rows`.  Per pivot:

@@ -9,6 +9,7 @@
 //   smx_shard.hpp     row-sharded exchange kernels
 //   smx_batch.hpp     k_copy (copy-ceiling probe), k_batch (one small LP per wavefront)
 //   smx_batch_wg.hpp  k_batch_wg (one mid-sized LP per workgroup, tableau in LDS)
+//   smx_batch_gm.hpp  k_batch_gm (one LP past the LDS edge per workgroup, tableau in global memory)
 //   smx_resident.hpp  k_resident: the whole pivot loop in one persistent launch, tableau in LDS
 //   smx_block.hpp     k_blk_*: P pivots per HBM sweep, decisions planned from the sweep's input
 // and this file holds the host side: grid sizing, variants, chains, graphs, RCCL, the C ABI.
@@ -53,6 +54,7 @@ static_assert(sizeof(smx_part) == 32, "smx_part layout");
 #include "smx_shard.hpp"
 #include "smx_batch.hpp"
 #include "smx_batch_wg.hpp"
+#include "smx_batch_gm.hpp"
 #include "smx_resident.hpp"
 #include "smx_block.hpp"
 #include "smx_window.hpp"
@@ -1183,6 +1185,55 @@ int smx_batch_solve_wg(const double* tabs, const int32_t* dims, int32_t B, int32
                        tabs, dims, B, Rmax, ldb, (int)wg_ldl(ldb), max_pivots, out, rc, xv, snaps,
                        status, npivots);
     return (int)hipGetLastError();
+}
+
+
+// ---- batched LPs past one CU's LDS (smx_batch_gm.hpp) ----------------------------------------
+// The envelope: the LDS vectors (with the mirrors, 16 * (Rmax + ldb) bytes) within 128 KiB, which
+// leaves room for the static reduction partials and takes every shape k_batch_wg takes (its
+// thinnest is 2 x 6783), and the table within kGmMaxElems elements -- the cap DESIGN 9.2 sets by
+// measurement against the one-by-one path (724 x 724 still wins there; nothing larger was tried).
+// The defaults of the three knobs are the winners of the A/B in DESIGN 9.2.
+namespace {
+
+constexpr int64_t kGmMaxSum = 8192;
+constexpr int64_t kGmMaxElems = (int64_t)1 << 19;
+
+inline bool gm_fits(int64_t Rmax, int64_t ldb) {
+    return Rmax >= 2 && ldb >= 2 && Rmax + ldb <= kGmMaxSum && Rmax * ldb <= kGmMaxElems;
+}
+
+int g_gm_block = 1024;   // smx_tune_batch_gm
+int g_gm_mirrors = 0;
+int g_gm_unroll = 8;
+
+}  // namespace
+
+int smx_batch_gm_fits(int32_t Rmax, int32_t ldb) { return gm_fits(Rmax, ldb) ? 1 : 0; }
+
+int smx_tune_batch_gm(int32_t block, int32_t mirrors, int32_t unroll) {
+    const int prev = g_gm_block | (g_gm_mirrors << 16) | (g_gm_unroll << 20);
+    if (block == 256 || block == 512 || block == 1024) g_gm_block = block;
+    if (mirrors == 0 || mirrors == 1) g_gm_mirrors = mirrors;
+    if (unroll == 1 || unroll == 4 || unroll == 8) g_gm_unroll = unroll;
+    return prev;
+}
+
+int smx_batch_solve_gm(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                       int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                       double* snaps, int32_t* status, int32_t* npivots, void* stream) {
+    if (B < 0 || Rmax < 2 || ldb < 2 || max_pivots < 0 || !gm_fits(Rmax, ldb))
+        return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    GmLaunch* launch;
+    if (g_gm_mirrors)
+        launch = g_gm_unroll == 8 ? launch_batch_gm<true, 8>
+                 : g_gm_unroll == 4 ? launch_batch_gm<true, 4> : launch_batch_gm<true, 1>;
+    else
+        launch = g_gm_unroll == 8 ? launch_batch_gm<false, 8>
+                 : g_gm_unroll == 4 ? launch_batch_gm<false, 4> : launch_batch_gm<false, 1>;
+    return launch(g_gm_block, (int)(16 * kGmMaxSum), tabs, dims, B, Rmax, ldb, max_pivots, out, rc,
+                  xv, snaps, status, npivots, S(stream));
 }
 
 

@@ -9,8 +9,11 @@ wavefront of ``k_batch`` (csrc/smx_batch.hpp).  Per problem the result is exactl
 ``ValueError`` outcomes.  Problems past that envelope whose table still fits one CU's LDS (to
 about 140 x 140, 300 x 40 or 40 x 300) run one workgroup each in ``k_batch_wg``
 (csrc/smx_batch_wg.hpp), grouped into launches of similar size (``wg_launches``).  Problems
-outside both envelopes (bigger, ragged, int entries, or with a ``len(function)`` the reference
-would index out of range) go through ``SimplexMethod`` one by one -- still on the device.
+past the LDS edge, up to a 724 x 724 table, run one workgroup each with the table in global memory
+(``k_batch_gm``, csrc/smx_batch_gm.hpp; launches from ``gm_launches``) once a call holds
+``GM_MIN_BATCH`` of them.  Problems outside all three envelopes (bigger, ragged, int entries, or
+with a ``len(function)`` the reference would index out of range) go through ``SimplexMethod``
+one by one -- still on the device.
 """
 from __future__ import annotations
 
@@ -28,12 +31,20 @@ from .engine import MESSAGES, Error, Info, SimplexMethod
 MAX_ROWS = 64      # one wavefront: rows 0..n (f-row = lane n)
 MAX_COLS = 64      # register-resident row of at most 64 doubles
 
-KERNELS = ("auto", "wave", "workgroup")
+KERNELS = ("auto", "wave", "workgroup", "global")
 ENVELOPE_ERROR = "a problem is outside the batch kernel's envelope"
 # history=True: one workgroup launch's snapshot buffer ([B][max_pivots][Rmax][ldb] doubles; a
 # 128 x 128 LP with max_pivots=256 is 32 MiB) stays under this many bytes -- a bucket is split
 # into as many launches as that takes (a single LP is never split).
 SNAP_BUDGET = 1 << 30
+# One global-memory launch's tables ([B][Rmax][ldb] doubles, in and out each) stay under this.
+GM_TABLE_BUDGET = 1 << 30
+# solve_batch(kernel="auto") takes the global-memory kernel only when a call holds at least this
+# many problems routed "global"; fewer go through SimplexMethod one by one.  The smallest measured
+# batch at which the kernel path's wall time per LP is at or under the one-by-one path's at every
+# measured shape inside the envelope (profiles/batch_gm.json): a single LP already is,
+# by 10 to 23 % of that path's best time at tables of 142^2, 256^2, 512^2 and 724^2.
+GM_MIN_BATCH = 1
 
 
 def wg_lds_bytes(Rmax: int, ldb: int) -> int:
@@ -42,6 +53,14 @@ def wg_lds_bytes(Rmax: int, ldb: int) -> int:
     if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
         return -1
     return int(_lib.load().smx_batch_wg_lds_bytes(int(Rmax), int(ldb)))
+
+
+def gm_fits(Rmax: int, ldb: int) -> bool:
+    """Whether a launch of Rmax x ldb blocks is inside k_batch_gm's envelope (the library is the
+    one source of the rule)."""
+    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
+        return False
+    return bool(_lib.load().smx_batch_gm_fits(int(Rmax), int(ldb)))
 
 
 def _shape(cons, func):
@@ -71,24 +90,35 @@ def _eligible(cons, func) -> bool:
 
 def route(constraints, function) -> str:
     """Where ``solve_batch`` sends a problem: ``"wave"`` (k_batch, one wavefront per LP),
-    ``"workgroup"`` (k_batch_wg, one workgroup per LP, tableau in LDS) or ``"single"``
-    (``SimplexMethod``, one by one: int entries, ragged rows, tables past one CU's LDS and the
-    reference's IndexError cases).  Host only."""
+    ``"workgroup"`` (k_batch_wg, one workgroup per LP, tableau in LDS), ``"global"`` (k_batch_gm,
+    one workgroup per LP, tableau in global memory: past one CU's LDS and inside
+    ``smx_batch_gm_fits``) or ``"single"`` (``SimplexMethod``, one by one: int entries, ragged
+    rows, tables past the global-memory kernel's envelope and the reference's IndexError cases).
+    Host only."""
     if _eligible(constraints, function):
         return "wave"
     shp = _shape(constraints, function)
-    if (shp is not None and wg_lds_bytes(shp[0] + 1, shp[1] + 1) >= 0
-            and not _has_ints(constraints, function)):
-        return "workgroup"
+    if shp is None:
+        return "single"
+    if wg_lds_bytes(shp[0] + 1, shp[1] + 1) >= 0:
+        return "single" if _has_ints(constraints, function) else "workgroup"
+    if gm_fits(shp[0] + 1, shp[1] + 1) and not _has_ints(constraints, function):
+        return "global"
     return "single"
 
 
 def choose_kernel(Rmax: int, ldb: int, kernel: str = "auto") -> str:
     """The kernel a launch of Rmax x ldb blocks runs on: ``"auto"`` takes the wave kernel inside
-    its envelope and the workgroup kernel past it; ``"wave"`` / ``"workgroup"`` force one.
+    its envelope and the workgroup kernel past it; ``"wave"`` / ``"workgroup"`` / ``"global"``
+    force one.  ``"auto"`` never answers ``"global"``: past the LDS edge it refuses, and the
+    global-memory kernel is reached only by name.
     Raises ValueError when the shape fits none of the kernels allowed."""
     if kernel not in KERNELS:
         raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    if kernel == "global":
+        if gm_fits(Rmax, ldb):
+            return "global"
+        raise ValueError(ENVELOPE_ERROR)
     if kernel != "workgroup" and Rmax <= MAX_ROWS and ldb <= MAX_COLS:
         return "wave"
     if kernel != "wave" and wg_lds_bytes(Rmax, ldb) >= 0:
@@ -135,8 +165,11 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
     0..m_k; ``dims``: int32 [B][3] = (n, m, len(function)) with every problem inside the kernel's
     envelope (see ``route``).  ``kernel``: ``"auto"`` runs the launch on the wave kernel when
     Rmax <= 64 and ldb <= 64 and on the workgroup kernel past that, up to what one CU's LDS
-    holds; ``"wave"`` / ``"workgroup"`` force one (``choose_kernel``).  A shape that fits none
-    raises ValueError.  Returns numpy arrays: ``final`` (same layout as tabs),
+    holds; ``"wave"`` / ``"workgroup"`` force one (``choose_kernel``).  ``"global"`` runs the
+    launch on the global-memory kernel at any shape inside ``smx_batch_gm_fits`` (to 724 x 724);
+    ``"auto"`` still refuses a shape past the LDS edge, so this API reaches that tier only by
+    name.  A shape that fits none raises ValueError.
+    Returns numpy arrays: ``final`` (same layout as tabs),
     ``status`` (SMX_* codes; SMX_PIVOT = max_pivots reached), ``npivots``, ``rc`` [B][P][2],
     ``xv`` [B][P][2] (x1, x2 after each pivot) and, with ``history``, ``snaps``
     [sum(npivots)][Rmax][ldb] -- problem k's tables after each of its pivots are
@@ -155,8 +188,9 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
         raise ValueError(ENVELOPE_ERROR)
     P = int(max_pivots)
     L = _lib.load()
-    solve, what = ((L.smx_batch_solve, "smx_batch_solve") if which == "wave" else
-                   (L.smx_batch_solve_wg, "smx_batch_solve_wg"))
+    solve, what = {"wave": (L.smx_batch_solve, "smx_batch_solve"),
+                   "workgroup": (L.smx_batch_solve_wg, "smx_batch_solve_wg"),
+                   "global": (L.smx_batch_solve_gm, "smx_batch_solve_gm")}[which]
     dev = torch.device(device if device is not None else "cuda")
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
@@ -230,6 +264,37 @@ def wg_launches(shapes, max_pivots: int, history: bool):
     return launches
 
 
+def gm_launches(shapes, max_pivots: int, history: bool):
+    """Split global-memory-kernel problems into launches; ``shapes[q]`` = (n, m) of problem q,
+    the result is a list of index lists.
+
+    The idea of ``wg_launches`` with the element count in place of the LDS footprint: sort by
+    (n + 1) * (m + 1); a launch takes the next problem while its padded Rmax x ldb still fits the
+    kernel (``gm_fits``) and stays within twice the element count of its smallest (first) member.
+    A launch ends where its tables (B * Rmax * ldb * 8 bytes) would pass ``GM_TABLE_BUDGET`` or,
+    with ``history``, where its snapshot buffer would pass ``SNAP_BUDGET``; a single LP is never
+    split."""
+    order = sorted(range(len(shapes)), key=lambda q: (shapes[q][0] + 1) * (shapes[q][1] + 1))
+    launches = []
+    cur, R, C, floor = [], 0, 0, 0
+    for q in order:
+        n, m = shapes[q]
+        R2, C2 = max(R, n + 1), max(C, m + 1)
+        tab = (len(cur) + 1) * R2 * C2 * 8
+        snap = tab * max(int(max_pivots), 1) if history else 0
+        if cur and (not gm_fits(R2, C2) or R2 * C2 > 2 * floor or tab > GM_TABLE_BUDGET
+                    or snap > SNAP_BUDGET):
+            launches.append(cur)
+            cur, R2, C2 = [], n + 1, m + 1
+        if not cur:
+            floor = R2 * C2
+        cur.append(q)
+        R, C = R2, C2
+    if cur:
+        launches.append(cur)
+    return launches
+
+
 def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=None,
                 kernel: str = "auto"):
     """Solve every ``(constraints, function)``; returns ``(results, statuses)``.
@@ -240,9 +305,13 @@ def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=No
     ``"cap"`` (``max_pivots`` reached) or ``"exception"``.
 
     Each problem goes where ``route`` says: the wave problems in one launch, the workgroup
-    problems in the launches of ``wg_launches``, the rest through ``SimplexMethod`` one by one.
+    problems in the launches of ``wg_launches``, the global problems in the launches of
+    ``gm_launches`` when the call holds at least ``GM_MIN_BATCH`` of them, the rest through
+    ``SimplexMethod`` one by one.
     ``kernel="workgroup"`` sends the wave problems through the workgroup kernel too;
-    ``kernel="wave"`` raises ValueError if a problem needs the workgroup kernel."""
+    ``kernel="wave"`` raises ValueError if a problem needs the workgroup kernel; both leave the
+    global problems to ``SimplexMethod``.  ``kernel="global"`` sends the wave and workgroup
+    problems through the global-memory kernel too, whatever their number."""
     problems = list(problems)
     if kernel not in KERNELS:
         raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
@@ -255,6 +324,10 @@ def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=No
         raise ValueError(ENVELOPE_ERROR)
     if kernel == "workgroup":
         routes = ["workgroup" if r == "wave" else r for r in routes]
+    if kernel == "global":
+        routes = [r if r == "single" else "global" for r in routes]
+    elif kernel != "auto" or routes.count("global") < GM_MIN_BATCH:
+        routes = ["single" if r == "global" else r for r in routes]
     for k, (c, f) in enumerate(problems):
         if routes[k] == "single":
             results[k], statuses[k] = _fallback(c, f, max_pivots, history)
@@ -267,6 +340,11 @@ def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=No
         shapes = [(len(problems[k][0]), len(problems[k][0][0]) - 1) for k in idx]
         launches += [("workgroup", [idx[q] for q in part])
                      for part in wg_launches(shapes, max_pivots, history)]
+    idx = [k for k, r in enumerate(routes) if r == "global"]
+    if idx:
+        shapes = [(len(problems[k][0]), len(problems[k][0][0]) - 1) for k in idx]
+        launches += [("global", [idx[q] for q in part])
+                     for part in gm_launches(shapes, max_pivots, history)]
     P = int(max_pivots)
     for which, idx in launches:
         tabs, dims = pack([problems[k] for k in idx])
