@@ -8,7 +8,8 @@
 //   smx_update.hpp    k_update: recalculate_matrix (simplex.py:143-177), every mode
 //   smx_shard.hpp     row-sharded exchange kernels
 //   smx_batch.hpp     k_copy (copy-ceiling probe), k_batch (one small LP per wavefront)
-//   smx_batch_wg.hpp  k_batch_wg (one mid-sized LP per workgroup, tableau in LDS)
+//   smx_batch_wg.hpp  wg_pivot_loop (the get_solution loop of one workgroup on one LP) and
+//                     k_batch_wg (one mid-sized LP per workgroup, tableau in LDS)
 //   smx_batch_gm.hpp  k_batch_gm (one LP past the LDS edge per workgroup, tableau in global memory)
 //   smx_resident.hpp  k_resident: the whole pivot loop in one persistent launch, tableau in LDS
 //   smx_block.hpp     k_blk_*: P pivots per HBM sweep, decisions planned from the sweep's input
@@ -1142,6 +1143,10 @@ int smx_batch_solve(const double* tabs, const int32_t* dims, int32_t B, int32_t 
 // under 1 KiB) -- the kResLdsMax precedent.
 namespace {
 
+// What both workgroup-per-LP entry points ask of a call beyond their envelope (wg_lds_bytes,
+// gm_fits: each refuses Rmax < 2 or ldb < 2 itself).
+inline bool wg_args_ok(int B, int max_pivots) { return B >= 0 && max_pivots >= 0; }
+
 constexpr int64_t kWgLdsMax = 160 * 1024 - 1024;
 
 inline int64_t wg_ldl(int64_t ldb) { return ldb | 1; }
@@ -1170,17 +1175,10 @@ int64_t smx_batch_wg_lds_bytes(int32_t Rmax, int32_t ldb) { return wg_lds_bytes(
 int smx_batch_solve_wg(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
                        int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
                        double* snaps, int32_t* status, int32_t* npivots, void* stream) {
-    if (B < 0 || Rmax < 2 || ldb < 2 || max_pivots < 0) return (int)hipErrorInvalidValue;
     const int64_t lds = wg_lds_bytes(Rmax, ldb);
-    if (lds < 0) return (int)hipErrorInvalidValue;
+    if (!wg_args_ok(B, max_pivots) || lds < 0) return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)k_batch_wg,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgLdsMax);
-    });
-    if (attr_err != hipSuccess) return (int)attr_err;
+    if (const int err = wg_raise_lds_limit<k_batch_wg>((int)kWgLdsMax)) return err;
     hipLaunchKernelGGL(k_batch_wg, dim3(B), dim3(wg_block(Rmax, ldb)), (size_t)lds, S(stream),
                        tabs, dims, B, Rmax, ldb, (int)wg_ldl(ldb), max_pivots, out, rc, xv, snaps,
                        status, npivots);
@@ -1222,8 +1220,7 @@ int smx_tune_batch_gm(int32_t block, int32_t mirrors, int32_t unroll) {
 int smx_batch_solve_gm(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
                        int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
                        double* snaps, int32_t* status, int32_t* npivots, void* stream) {
-    if (B < 0 || Rmax < 2 || ldb < 2 || max_pivots < 0 || !gm_fits(Rmax, ldb))
-        return (int)hipErrorInvalidValue;
+    if (!wg_args_ok(B, max_pivots) || !gm_fits(Rmax, ldb)) return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
     GmLaunch* launch;
     if (g_gm_mirrors)

@@ -233,66 +233,55 @@ def pack(problems):
     return tabs, dims
 
 
-def wg_launches(shapes, max_pivots: int, history: bool):
-    """Split workgroup-kernel problems into launches; ``shapes[q]`` = (n, m) of problem q, the
-    result is a list of index lists.
-
-    A launch pads every member to its largest rows x columns, and that padded block is what each
-    workgroup holds in LDS, so one big member would cost all the others occupancy.  The rule: sort
-    by own LDS footprint (``wg_lds_bytes(n + 1, m + 1)``); a launch takes the next problem while
-    its padded footprint still fits the kernel and stays within twice the footprint of its
-    smallest (first) member.  With ``history`` a launch also ends where its snapshot buffer
-    would pass ``SNAP_BUDGET``."""
-    order = sorted(range(len(shapes)), key=lambda q: wg_lds_bytes(shapes[q][0] + 1,
-                                                                 shapes[q][1] + 1))
+def _split_launches(shapes, max_pivots, history, cost, table_budget=None):
+    """The launch splitter of ``wg_launches`` and ``gm_launches``.  ``cost(R, C)`` is what a
+    launch of R x C blocks costs per problem, negative where the kernel does not take the shape.
+    Sort the problems by their own cost; a launch takes the next problem while its padded
+    rows x columns still fit the kernel and cost at most twice its smallest (first) member.  A
+    launch also ends where its tables (B * Rmax * ldb * 8 bytes) would pass ``table_budget`` or,
+    with ``history``, where its snapshot buffer would pass ``SNAP_BUDGET``; a single LP is never
+    split."""
+    order = sorted(range(len(shapes)), key=lambda q: cost(shapes[q][0] + 1, shapes[q][1] + 1))
     launches = []
     cur, R, C, floor = [], 0, 0, 0
     for q in order:
         n, m = shapes[q]
         R2, C2 = max(R, n + 1), max(C, m + 1)
-        lds = wg_lds_bytes(R2, C2)
-        snap = (len(cur) + 1) * max(int(max_pivots), 1) * R2 * C2 * 8 if history else 0
-        if cur and (lds < 0 or lds > 2 * floor or snap > SNAP_BUDGET):
+        padded = cost(R2, C2)
+        tab = (len(cur) + 1) * R2 * C2 * 8
+        snap = tab * max(int(max_pivots), 1) if history else 0
+        if cur and (not 0 <= padded <= 2 * floor or snap > SNAP_BUDGET
+                    or (table_budget is not None and tab > table_budget)):
             launches.append(cur)
             cur, R2, C2 = [], n + 1, m + 1
+            padded = cost(R2, C2)
         if not cur:
-            floor = wg_lds_bytes(R2, C2)
+            floor = padded
         cur.append(q)
         R, C = R2, C2
     if cur:
         launches.append(cur)
     return launches
+
+
+def wg_launches(shapes, max_pivots: int, history: bool):
+    """Split workgroup-kernel problems into launches; ``shapes[q]`` = (n, m) of problem q, the
+    result is a list of index lists.
+
+    A launch pads every member to its largest rows x columns, and that padded block is what each
+    workgroup holds in LDS, so one big member would cost all the others occupancy.  The rule is
+    ``_split_launches`` with the LDS footprint (``wg_lds_bytes``) as the cost."""
+    return _split_launches(shapes, max_pivots, history, wg_lds_bytes)
 
 
 def gm_launches(shapes, max_pivots: int, history: bool):
     """Split global-memory-kernel problems into launches; ``shapes[q]`` = (n, m) of problem q,
     the result is a list of index lists.
 
-    The idea of ``wg_launches`` with the element count in place of the LDS footprint: sort by
-    (n + 1) * (m + 1); a launch takes the next problem while its padded Rmax x ldb still fits the
-    kernel (``gm_fits``) and stays within twice the element count of its smallest (first) member.
-    A launch ends where its tables (B * Rmax * ldb * 8 bytes) would pass ``GM_TABLE_BUDGET`` or,
-    with ``history``, where its snapshot buffer would pass ``SNAP_BUDGET``; a single LP is never
-    split."""
-    order = sorted(range(len(shapes)), key=lambda q: (shapes[q][0] + 1) * (shapes[q][1] + 1))
-    launches = []
-    cur, R, C, floor = [], 0, 0, 0
-    for q in order:
-        n, m = shapes[q]
-        R2, C2 = max(R, n + 1), max(C, m + 1)
-        tab = (len(cur) + 1) * R2 * C2 * 8
-        snap = tab * max(int(max_pivots), 1) if history else 0
-        if cur and (not gm_fits(R2, C2) or R2 * C2 > 2 * floor or tab > GM_TABLE_BUDGET
-                    or snap > SNAP_BUDGET):
-            launches.append(cur)
-            cur, R2, C2 = [], n + 1, m + 1
-        if not cur:
-            floor = R2 * C2
-        cur.append(q)
-        R, C = R2, C2
-    if cur:
-        launches.append(cur)
-    return launches
+    ``_split_launches`` with the element count (n + 1) * (m + 1) inside ``gm_fits`` as the cost
+    and ``GM_TABLE_BUDGET`` on a launch's tables."""
+    return _split_launches(shapes, max_pivots, history,
+                           lambda R, C: R * C if gm_fits(R, C) else -1, GM_TABLE_BUDGET)
 
 
 def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=None,
@@ -335,16 +324,12 @@ def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=No
     idx = [k for k, r in enumerate(routes) if r == "wave"]
     if idx:
         launches.append(("wave", idx))
-    idx = [k for k, r in enumerate(routes) if r == "workgroup"]
-    if idx:
-        shapes = [(len(problems[k][0]), len(problems[k][0][0]) - 1) for k in idx]
-        launches += [("workgroup", [idx[q] for q in part])
-                     for part in wg_launches(shapes, max_pivots, history)]
-    idx = [k for k, r in enumerate(routes) if r == "global"]
-    if idx:
-        shapes = [(len(problems[k][0]), len(problems[k][0][0]) - 1) for k in idx]
-        launches += [("global", [idx[q] for q in part])
-                     for part in gm_launches(shapes, max_pivots, history)]
+    for which, split in (("workgroup", wg_launches), ("global", gm_launches)):
+        idx = [k for k, r in enumerate(routes) if r == which]
+        if idx:
+            shapes = [(len(problems[k][0]), len(problems[k][0][0]) - 1) for k in idx]
+            launches += [(which, [idx[q] for q in part])
+                         for part in split(shapes, max_pivots, history)]
     P = int(max_pivots)
     for which, idx in launches:
         tabs, dims = pack([problems[k] for k in idx])

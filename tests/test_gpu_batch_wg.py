@@ -2,19 +2,18 @@
 oracle, the reference's fixtures and SimplexMethod."""
 from __future__ import annotations
 
-import functools
 import random
-from collections import Counter, defaultdict
+from collections import Counter
 
 import numpy as np
 import pytest
 
-from golden_util import (dec, dec_input, dec_table, load, same_table, same_value, table_hash,
-                         trajectory_cap, trajectory_cases)
+from batch_util import (OUTCOME, case, no_fallback as _no_fallback,
+                        same_as_oracle as _same_as_oracle, same_solution as _same_solution,
+                        solve as _solve, trajectory_fixtures_through, xv_follows_the_labels)
+from golden_util import dec, dec_input, dec_table, load, same_table, same_value
 
 pytestmark = pytest.mark.gpu
-
-OUTCOME = {0: "cap", 1: "optimum", 2: "incorrect", 3: "not_converge"}
 
 # kind, n, m, cap, the C oracle's outcomes over seeds 0..15 (run on the CPU when this file was
 # written; every final table finite)
@@ -45,39 +44,8 @@ def _flen(kind, n, m, seed):
     return m + 1 if (kind, n, m) == ("uniform", 65, 65) and seed % 2 else m
 
 
-@functools.lru_cache(maxsize=None)
 def _case(kind, n, m, seed, cap):
-    """(T, flen, oracle final table, status, pivots, log), computed once and shared."""
-    from oracle import c_oracle
-    from simplex_mi355x import lp
-    T = lp.dense_tableau(kind, seed, n, m)
-    flen = _flen(kind, n, m, seed)
-    Tref, st, done, log = c_oracle.run(T, n, m, flen, cap)
-    for a in (T, Tref, log):
-        a.setflags(write=False)
-    return T, flen, Tref, st, done, log
-
-
-def _solve(cases, cap, Rmax=None, ldb=None, **kw):
-    """cases: [(T, n, m, flen)] -> solve_batch_arrays output of one launch."""
-    from simplex_mi355x.batch import solve_batch_arrays
-    Rmax = Rmax or max(n for _, n, _, _ in cases) + 1
-    ldb = ldb or max(m for _, _, m, _ in cases) + 1
-    tabs = np.zeros((len(cases), Rmax, ldb))
-    dims = np.zeros((len(cases), 3), dtype=np.int32)
-    for q, (T, n, m, flen) in enumerate(cases):
-        tabs[q, :n + 1, :m + 1] = T
-        dims[q] = (n, m, flen)
-    return solve_batch_arrays(tabs, dims, cap, **kw)
-
-
-def _same_as_oracle(out, q, n, m, ref, what):
-    _, _, Tref, st, done, log = ref
-    assert int(out["status"][q]) == st, what
-    assert int(out["npivots"][q]) == done, what
-    assert np.array_equal(out["rc"][q, :done], log), what
-    got = np.ascontiguousarray(out["final"][q, :n + 1, :m + 1])
-    assert np.array_equal(got.view(np.int64), Tref[:n + 1].view(np.int64)), what
+    return case(kind, n, m, seed, cap, _flen(kind, n, m, seed))
 
 
 @pytest.mark.parametrize("kind,n,m,cap,expect", SHAPES,
@@ -141,47 +109,9 @@ def test_envelope_edge():
             solve_batch_arrays(tabs, dims, 64, kernel=kernel)
 
 
-def _no_fallback(monkeypatch):
-    from simplex_mi355x import batch
-
-    def boom(*a, **k):
-        raise AssertionError("a problem left the batch kernels")
-    monkeypatch.setattr(batch, "_fallback", boom)
-
-
 def test_trajectory_fixtures_through_workgroup_kernel(monkeypatch):
-    """Every capped trajectory fixture the batch kernels can take, forced through k_batch_wg:
-    per-step table hashes, (i, j), x1 / x2 / optimum, final labels and the outcome -- the
-    NaN-first rule, the ties and the signed zeros of ties.json / edge.json on the new code."""
-    from simplex_mi355x.batch import route, solve_batch
-    import simplex
-    _no_fallback(monkeypatch)
-    groups = defaultdict(list)
-    for label, cons, func, rec in trajectory_cases():
-        if route(cons, func) != "single":
-            groups[trajectory_cap(rec)].append((label, cons, func, rec))
-    checked = 0
-    for cap, cases in groups.items():
-        results, statuses = solve_batch([(c, f) for _, c, f, _ in cases], max_pivots=cap,
-                                        history=True, kernel="workgroup")
-        for (label, cons, func, rec), got, st in zip(cases, results, statuses):
-            outcome = rec["outcome"]
-            assert outcome["kind"] != "exception", label     # route sends those to "single"
-            infos = [g for g in got if isinstance(g, simplex.Info)]
-            assert [table_hash(i.table) for i in infos] == [s["hash"] for s in rec["steps"]], label
-            for i, s in zip(infos, rec["steps"]):
-                assert (i.i, i.j) == (s.get("i"), s.get("j")), label
-                for key in ("x1", "x2", "optimum"):
-                    assert same_value(getattr(i, key), dec(s[key])), (label, key)
-            if outcome["kind"] == "error":
-                assert str(got[-1]) == outcome["message"] and st == "error"
-            elif outcome["kind"] == "optimum":
-                assert st == "optimum"
-            else:
-                assert st == "cap"
-            assert infos[-1].row == rec["row"] and infos[-1].column == rec["column"]
-            checked += 1
-    assert checked > 200
+    """batch_util.trajectory_fixtures_through on k_batch_wg."""
+    trajectory_fixtures_through("workgroup", monkeypatch)
 
 
 def test_examples_through_workgroup_kernel(monkeypatch):
@@ -220,19 +150,6 @@ def test_history_snapshots_replay_the_oracle_log():
         for k, (r, c) in enumerate(log):
             cur = c_oracle.pivot(cur, int(r), int(c))
             assert np.array_equal(snaps[k].view(np.int64), cur.view(np.int64)), (q, k)
-
-
-def _same_solution(got, exp, what):
-    import simplex
-    assert len(got) == len(exp), what
-    for g, e in zip(got, exp):
-        if isinstance(e, simplex.Error):
-            assert isinstance(g, simplex.Error) and str(g) == str(e), what
-            continue
-        assert (g.row, g.column, g.i, g.j) == (e.row, e.column, e.i, e.j), what
-        assert same_table(g.table, e.table), what
-        for key in ("x1", "x2", "optimum"):
-            assert same_value(getattr(g, key), getattr(e, key)), (what, key)
 
 
 @pytest.mark.parametrize("history", [True, False])
@@ -283,16 +200,4 @@ def test_arrays_api_takes_66_by_66():
     assert out["final"].shape == (16, 66, 66)
     assert out["rc"].shape == (16, 1024, 2) and out["xv"].shape == (16, 1024, 2)
     assert [int(v) for v in out["npivots"]] == [r[4] for r in refs]
-    # x1, x2 after the last pivot: the "-b" entry of the row that holds the label, else 0
-    for q, (T, flen, Tref, st, done, log) in enumerate(refs):
-        where = {0: ("col", 0), 1: ("col", 1)}               # labels 'x1', 'x2' (simplex.py:152)
-        for r, c in log:
-            for lab, (side, at) in list(where.items()):
-                if side == "col" and at == c:
-                    where[lab] = ("row", int(r))
-                elif side == "row" and at == r:
-                    where[lab] = ("col", int(c))
-        for lab in (0, 1):
-            side, at = where[lab]
-            want = Tref[at, 65] if side == "row" else 0.0
-            assert same_value(float(out["xv"][q, done - 1, lab]), float(want)), (q, lab)
+    xv_follows_the_labels(out, refs, 65)

@@ -17,79 +17,30 @@ Batch sizes are bounded by the launch's table budget (batch.GM_TABLE_BUDGET); th
 timing, which holds every table as Python lists, stops at 2^24 table elements per call.  The LPs
 of a batch are seeds 0..15 repeated.  Run one process at a time on one box; `--out FILE` appends
 the lines to FILE as well."""
-import json
-import os
 import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "simplex-method-solver_amd")]
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import batch_bench_util as util
+from batch_bench_util import CAP, emit, problems
 
 SHAPES = ((141, 141), (255, 255), (511, 511), (723, 723))   # tables of 142^2, 256^2, 512^2, 724^2
 BATCHES = (1, 4, 16, 256, 1024)
-CAP = 256
 DISTINCT = 16
 LIST_ELEMS = 1 << 24
 REPS = 5
 
 
 def timed(call, reps=REPS):
-    """Wall seconds of `call` (synchronised), `reps` times: (median, least, the last result)."""
-    walls = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        ret = call()
-        torch.cuda.synchronize()
-        walls.append(time.perf_counter() - t0)
-    return float(np.median(walls)), min(walls), ret
+    return util.timed(call, reps)
 
 
 def tables(B, n, m):
-    from simplex_mi355x import lp
-    base = np.stack([lp.dense_tableau("uniform", s, n, m) for s in range(min(B, DISTINCT))])
-    tabs = np.ascontiguousarray(np.resize(base, (B, n + 1, m + 1)))
-    dims = np.tile(np.array([n, m, m], dtype=np.int32), (B, 1))
-    return tabs, dims
+    return util.tables(B, n, m, DISTINCT)
 
 
-def problems(tabs, n, m):
-    return [(t[:n].tolist(), t[n, :m].tolist()) for t in tabs]
-
-
-def emit(rec, out):
-    line = json.dumps(rec)
-    print(line, flush=True)
-    if out:
-        with open(out, "a") as fh:
-            fh.write(line + "\n")
-
-
-def kernel_ms(L, tabs, dims, n, m, reps):
-    """The kernel on resident buffers by HIP events: one warm-up launch, then `reps` back to back.
-    Returns (ms per launch, pivots of one launch, most pivots of one LP)."""
-    from simplex_mi355x import _lib
-    B = len(tabs)
-    dt, dd = torch.from_numpy(tabs).cuda(), torch.from_numpy(dims).cuda()
-    o = torch.empty_like(dt)
-    rc = torch.zeros((B, CAP, 2), dtype=torch.int32, device="cuda")
-    xv = torch.zeros((B, CAP, 2), dtype=torch.float64, device="cuda")
-    s_ = torch.zeros(B, dtype=torch.int32, device="cuda")
-    np_ = torch.zeros(B, dtype=torch.int32, device="cuda")
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a = (dt.data_ptr(), dd.data_ptr(), B, n + 1, m + 1, CAP, o.data_ptr(), rc.data_ptr(),
-         xv.data_ptr(), None, s_.data_ptr(), np_.data_ptr(),
-         torch.cuda.current_stream().cuda_stream)
-    _lib.check(L.smx_batch_solve_gm(*a), "smx_batch_solve_gm")
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        L.smx_batch_solve_gm(*a)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps, int(np_.sum().item()), int(np_.max().item())
+def kernel_ms(tabs, dims, n, m, reps):
+    """(ms per launch, pivots of one launch, most pivots of one LP)."""
+    kms, npiv = util.kernel_ms("smx_batch_solve_gm", tabs, dims, n, m, reps)
+    return kms, int(npiv.sum()), int(npiv.max())
 
 
 def serial(K, out):
@@ -120,7 +71,7 @@ def ab(out):
                     for mirrors in (1, 0):
                         for threads in (256, 512, 1024):
                             L.smx_tune_batch_gm(threads, mirrors, unroll)
-                            kms, pivots, deepest = kernel_ms(L, tabs, dims, n, m, 5)
+                            kms, pivots, deepest = kernel_ms(tabs, dims, n, m, 5)
                             emit({"what": "batch_gm_ab", "threads": threads, "mirrors": mirrors,
                                   "unroll": unroll, "shape": [n, m], "lps": B, "max_pivots": CAP,
                                   "kernel_ms": kms, "pivots": pivots,
@@ -131,11 +82,7 @@ def ab(out):
 
 def main():
     args = sys.argv[1:]
-    out = None
-    if "--out" in args:
-        k = args.index("--out")
-        out = args[k + 1]
-        del args[k:k + 2]
+    out = util.pop_out(args)
     if args and args[0] == "--serial":
         return serial(int(args[1]) if len(args) > 1 else 8, out)
     if args and args[0] == "--ab":
@@ -153,7 +100,7 @@ def main():
             if B * elems * 8 > batch.GM_TABLE_BUDGET:
                 continue
             tabs, dims = tables(B, n, m)
-            kms, pivots, deepest = kernel_ms(L, tabs, dims, n, m, 5 if B <= 256 else 2)
+            kms, pivots, deepest = kernel_ms(tabs, dims, n, m, 5 if B <= 256 else 2)
             rec = {"what": "batch_gm", "shape": [n, m], "lps": B, "max_pivots": CAP,
                    **cfg, "pivots": pivots, "kernel_ms": kms, "kernel_ms_per_lp": kms / B,
                    "us_per_step": 1e3 * kms / max(deepest, 1),

@@ -9,39 +9,14 @@ through solve_batch(history=False).
                                                   commit without the workgroup kernel that call
                                                   runs them one by one through SimplexMethod
 Run one process at a time on one box; `--out FILE` appends the lines to FILE as well."""
-import json
-import os
 import sys
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "simplex-method-solver_amd")]
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from batch_bench_util import CAP, emit, kernel_ms, pop_out, problems, tables
+import numpy as np
+import torch
 
 SHAPES = ((100, 100), (65, 65))
-CAP = 256
-
-
-def tables(B, n, m):
-    from simplex_mi355x import lp
-    tabs = np.zeros((B, n + 1, m + 1))
-    for s in range(B):
-        tabs[s] = lp.dense_tableau("uniform", s, n, m)
-    dims = np.tile(np.array([n, m, m], dtype=np.int32), (B, 1))
-    return tabs, dims
-
-
-def problems(tabs, n, m):
-    return [(t[:n].tolist(), t[n, :m].tolist()) for t in tabs]
-
-
-def emit(rec, out):
-    line = json.dumps(rec)
-    print(line, flush=True)
-    if out:
-        with open(out, "a") as fh:
-            fh.write(line + "\n")
 
 
 def serial(K, out):
@@ -64,17 +39,11 @@ def serial(K, out):
 
 def main():
     args = sys.argv[1:]
-    out = None
-    if "--out" in args:
-        k = args.index("--out")
-        out = args[k + 1]
-        del args[k:k + 2]
+    out = pop_out(args)
     if args and args[0] == "--serial":
         return serial(int(args[1]) if len(args) > 1 else 64, out)
-    from simplex_mi355x import _lib
     from simplex_mi355x.batch import solve_batch, solve_batch_arrays, wg_lds_bytes
     B = int(args[0]) if args else 2048
-    L = _lib.load()
     for n, m in SHAPES:
         tabs, dims = tables(B, n, m)
         solve_batch_arrays(tabs[:64], dims[:64], CAP)                         # warm
@@ -88,26 +57,9 @@ def main():
         t0 = time.perf_counter()
         solve_batch(probs, max_pivots=CAP, history=False)                     # Info-object API
         wall_infos = time.perf_counter() - t0
-        # device only: the kernel on resident buffers, timed with HIP events
-        dt, dd = torch.from_numpy(tabs).cuda(), torch.from_numpy(dims).cuda()
-        o = torch.empty_like(dt)
-        rc = torch.zeros((B, CAP, 2), dtype=torch.int32, device="cuda")
-        xv = torch.zeros((B, CAP, 2), dtype=torch.float64, device="cuda")
-        s_ = torch.zeros(B, dtype=torch.int32, device="cuda")
-        np_ = torch.zeros(B, dtype=torch.int32, device="cuda")
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a = (dt.data_ptr(), dd.data_ptr(), B, n + 1, m + 1, CAP, o.data_ptr(), rc.data_ptr(),
-             xv.data_ptr(), None, s_.data_ptr(), np_.data_ptr(),
-             torch.cuda.current_stream().cuda_stream)
-        _lib.check(L.smx_batch_solve_wg(*a), "smx_batch_solve_wg")
-        e0.record()
-        for _ in range(10):
-            L.smx_batch_solve_wg(*a)
-        e1.record()
-        torch.cuda.synchronize()
-        kms = e0.elapsed_time(e1) / 10
-        pivots = int(np_.sum().item())
-        assert np.array_equal(np_.cpu().numpy(), res["npivots"])
+        kms, npiv = kernel_ms("smx_batch_solve_wg", tabs, dims, n, m, 10)    # device only
+        pivots = int(npiv.sum())
+        assert np.array_equal(npiv, res["npivots"])
         codes = {0: "cap", 1: "optimum", 2: "incorrect system", 3: "does not converge"}
         emit({"what": "batch_wg", "shape": [n, m], "lps": B, "max_pivots": CAP,
               "lds_bytes": wg_lds_bytes(n + 1, m + 1), "pivots": pivots, "kernel_ms": kms,
