@@ -309,30 +309,26 @@ int launch_update(const double* Tin, double* Tout, const smx_shape& s, int parit
 // the all-gather they hide (profiles/r01_shard_overlap_trace.txt).
 int g_fused = 1;
 
+// ev (optional): 2 events per step recorded around its update launch.
 int launch_chain(double* buf0, double* buf1, const smx_shape& s, int parity, int k, smx_ctl* ctl,
-                 smx_part* parts, int32_t* log, double* xhist, int64_t log_cap, hipStream_t st) {
-    if (g_fused && k > 0) {
-        // prime the records of the first step, one fused kernel per pivot, publish the next
-        int err = launch_prime(parity ? buf1 : buf0, s, parity, ctl, parts, st);
-        if (err) return err;
-        for (int step = 0; step < k; ++step) {
-            const int p = (parity + step) & 1;
-            err = launch_update_mode<kFused>(p ? buf1 : buf0, p ? buf0 : buf1, s, p, ctl, parts,
-                                             log, xhist, log_cap, nullptr, 0, 0, st);
-            if (err) return err;
-        }
-        return launch_publish(s, (parity + k) & 1, ctl, parts, st);
-    }
-    for (int step = 0; step < k; ++step) {
+                 smx_part* parts, int32_t* log, double* xhist, int64_t log_cap, hipStream_t st,
+                 hipEvent_t* ev = nullptr) {
+    // fused: prime the records of the first step, one fused kernel per pivot, publish the next
+    const bool fused = g_fused && k > 0;
+    int err = fused ? launch_prime(parity ? buf1 : buf0, s, parity, ctl, parts, st) : 0;
+    for (int step = 0; step < k && !err; ++step) {
         const int p = (parity + step) & 1;
         double* tin = p ? buf1 : buf0;
         double* tout = p ? buf0 : buf1;
-        int err = launch_select(tin, s, p, ctl, parts, st);
-        if (err) return err;
-        err = launch_update(tin, tout, s, p, ctl, parts, log, xhist, log_cap, st);
-        if (err) return err;
+        if (!fused && (err = launch_select(tin, s, p, ctl, parts, st))) break;
+        if (ev) (void)hipEventRecord(ev[2 * step], st);
+        err = fused ? launch_update_mode<kFused>(tin, tout, s, p, ctl, parts, log, xhist, log_cap,
+                                                 nullptr, 0, 0, st)
+                    : launch_update(tin, tout, s, p, ctl, parts, log, xhist, log_cap, st);
+        if (ev) (void)hipEventRecord(ev[2 * step + 1], st);
     }
-    return 0;
+    if (!err && fused) err = launch_publish(s, (parity + k) & 1, ctl, parts, st);
+    return err;
 }
 
 // ---- on-chip resident pivot loop (smx_resident.hpp) ------------------------------------------
@@ -853,10 +849,50 @@ bool bshard_args_ok(const smx_shape* shape, int P, const void* blk, int64_t blk_
     return blk_bytes >= blk_layout(s.rows + 1, s.ld, blk_parts_of(s.nparts, s.rows)).bytes;
 }
 
+// What the chain entry points ask on top of them: two distinct buffers and a control block ...
+bool block_chain_ok(const smx_shape* shape, int k, int P, const void* blk, int64_t blk_bytes,
+                    const double* buf0, const double* buf1, const smx_ctl* ctl) {
+    return block_args_ok(shape, k, P, blk, blk_bytes) && buf0 != buf1 && ctl;
+}
+
+// ... and, row-sharded, the exchange buffers and the communicator
+bool bshard_chain_ok(const smx_shape* shape, int k, int P, const void* blk, int64_t blk_bytes,
+                     const double* buf0, const double* buf1, const smx_ctl* ctl,
+                     const double* send, const double* recv, int nranks, const void* comm) {
+    return bshard_args_ok(shape, P, blk, blk_bytes) && buf0 != buf1 && ctl && send && recv &&
+           nranks >= 1 && comm && k >= 0;
+}
+
 struct Graph {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
+    ~Graph() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+    }
 };
+
+// Close the capture begun on st (always, once it began), instantiate the graph and hand it out.
+// lerr: the error of the captured launches, which takes precedence over the end-capture error.
+// On any failure nothing is left behind and *graph_out is not written.
+int end_capture(hipStream_t st, int lerr, void** graph_out) {
+    Graph* g = new Graph();
+    const hipError_t e = hipStreamEndCapture(st, &g->graph);
+    int err = lerr ? lerr : (int)e;
+    if (!err) err = (int)hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
+    if (err)
+        delete g;
+    else
+        *graph_out = g;
+    return err;
+}
+
+// enqueue(): the launches of one chain on st, captured (thread-local mode) as a Graph
+template <class Enqueue>
+int capture_graph(hipStream_t st, void** graph_out, Enqueue enqueue) {
+    const hipError_t err = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+    return err != hipSuccess ? (int)err : end_capture(st, enqueue(), graph_out);
+}
 
 // Timing events of the *_run_timed calls: created once (smx_timer_reserve, or on first need) and
 // reused, so no hipEventCreate / hipEventDestroy runs inside a caller's timed region.
@@ -889,6 +925,35 @@ int timer_events(size_t n, hipEvent_t** out) {
     }
     *out = g_timer_ev;
     return 0;
+}
+
+// Events of a timed chain of n pairs (pivots or sweeps): ev[2i] / ev[2i+1] around pair i, recorded
+// by the chain; ev[2n] before the chain.  end_mark (the block forms): ev[2n+1] after the chain's
+// last launch closes the total; without it (the one-pivot forms) the last pair's closing event
+// does, so the publish launch is outside the total.
+int timed_read(int n, bool end_mark, float* pair_ms, float* total_ms) {
+    hipEvent_t* ev = g_timer_ev;
+    const hipEvent_t last = ev[end_mark ? 2 * n + 1 : 2 * n - 1];
+    const int err = (int)hipEventSynchronize(last);
+    if (!err) {
+        for (int i = 0; i < n; ++i)
+            (void)hipEventElapsedTime(&pair_ms[i], ev[2 * i], ev[2 * i + 1]);
+        (void)hipEventElapsedTime(total_ms, ev[2 * n], last);
+    }
+    return err;
+}
+
+// enqueue(ev): the launches of one chain on st with the pool's events; then the readout, unless
+// pair_ms is NULL (the deferred form: smx_block_timed_read reads later).
+template <class Enqueue>
+int run_timed(hipStream_t st, int n, bool end_mark, float* pair_ms, float* total_ms,
+              Enqueue enqueue) {
+    hipEvent_t* ev = nullptr;
+    if (timer_events((size_t)(2 * n + 1 + end_mark), &ev)) return (int)hipErrorOutOfMemory;
+    (void)hipEventRecord(ev[2 * n], st);
+    const int err = enqueue(ev);
+    if (end_mark) (void)hipEventRecord(ev[2 * n + 1], st);
+    return err || !pair_ms ? err : timed_read(n, end_mark, pair_ms, total_ms);
 }
 
 }  // namespace
@@ -1000,67 +1065,20 @@ int smx_run_timed(double* buf0, double* buf1, const smx_shape* shape, int32_t pa
                   void* stream, float* host_update_ms, float* host_total_ms) {
     if (!shape_ok(shape) || buf0 == buf1 || k < 1 || !host_update_ms || !host_total_ms)
         return (int)hipErrorInvalidValue;
-    hipStream_t st = S(stream);
-    const int p0 = parity & 1;
-    hipEvent_t* ev = nullptr;
-    int err = 0;
-    if (timer_events((size_t)(2 * k + 1), &ev)) return (int)hipErrorOutOfMemory;
-    (void)hipEventRecord(ev[2 * k], st);
-    if (g_fused) err = launch_prime(p0 ? buf1 : buf0, *shape, p0, ctl, parts, st);
-    for (int step = 0; step < k && !err; ++step) {
-        const int p = (p0 + step) & 1;
-        double* tin = p ? buf1 : buf0;
-        double* tout = p ? buf0 : buf1;
-        if (g_fused) {
-            (void)hipEventRecord(ev[2 * step], st);
-            err = launch_update_mode<kFused>(tin, tout, *shape, p, ctl, parts, log, xhist,
-                                             log_cap, nullptr, 0, 0, st);
-            (void)hipEventRecord(ev[2 * step + 1], st);
-            continue;
-        }
-        err = launch_select(tin, *shape, p, ctl, parts, st);
-        if (err) break;
-        (void)hipEventRecord(ev[2 * step], st);
-        err = launch_update(tin, tout, *shape, p, ctl, parts, log, xhist, log_cap, st);
-        (void)hipEventRecord(ev[2 * step + 1], st);
-    }
-    if (!err && g_fused) err = launch_publish(*shape, (p0 + k) & 1, ctl, parts, st);
-    if (!err) err = (int)hipEventSynchronize(ev[2 * k - 1]);
-    if (!err) {
-        for (int step = 0; step < k; ++step)
-            (void)hipEventElapsedTime(&host_update_ms[step], ev[2 * step], ev[2 * step + 1]);
-        (void)hipEventElapsedTime(host_total_ms, ev[2 * k], ev[2 * k - 1]);
-    }
-    return err;
+    return run_timed(S(stream), k, false, host_update_ms, host_total_ms, [&](hipEvent_t* ev) {
+        return launch_chain(buf0, buf1, *shape, parity & 1, k, ctl, parts, log, xhist, log_cap,
+                            S(stream), ev);
+    });
 }
 
 int smx_graph_create(double* buf0, double* buf1, const smx_shape* shape, int32_t parity,
                      int32_t k, smx_ctl* ctl, smx_part* parts, int32_t* log, double* xhist,
                      int64_t log_cap, void* stream, void** graph_out) {
     if (!shape_ok(shape) || buf0 == buf1 || k < 1 || !graph_out) return (int)hipErrorInvalidValue;
-    hipStream_t st = S(stream);
-    Graph* g = new Graph();
-    hipError_t err = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    if (err != hipSuccess) {
-        delete g;
-        return (int)err;
-    }
-    int lerr = launch_chain(buf0, buf1, *shape, parity & 1, k, ctl, parts, log, xhist, log_cap,
-                            st);
-    err = hipStreamEndCapture(st, &g->graph);
-    if (lerr || err != hipSuccess) {
-        if (g->graph) (void)hipGraphDestroy(g->graph);
-        delete g;
-        return lerr ? lerr : (int)err;
-    }
-    err = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
-    if (err != hipSuccess) {
-        (void)hipGraphDestroy(g->graph);
-        delete g;
-        return (int)err;
-    }
-    *graph_out = g;
-    return 0;
+    return capture_graph(S(stream), graph_out, [&] {
+        return launch_chain(buf0, buf1, *shape, parity & 1, k, ctl, parts, log, xhist, log_cap,
+                            S(stream));
+    });
 }
 
 int smx_graph_launch(void* graph, void* stream) {
@@ -1069,11 +1087,7 @@ int smx_graph_launch(void* graph, void* stream) {
 }
 
 int smx_graph_destroy(void* graph) {
-    if (!graph) return 0;
-    Graph* g = static_cast<Graph*>(graph);
-    if (g->exec) (void)hipGraphExecDestroy(g->exec);
-    if (g->graph) (void)hipGraphDestroy(g->graph);
-    delete g;
+    delete static_cast<Graph*>(graph);
     return 0;
 }
 
@@ -1117,23 +1131,13 @@ int smx_batch_solve(const double* tabs, const int32_t* dims, int32_t B, int32_t 
     if (B < 0 || Rmax < 1 || Rmax > kWave || ldb < 1 || ldb > 64 || max_pivots < 0)
         return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
-    const dim3 grid((B + 3) / 4), block(256);
-    hipStream_t st = S(stream);
-    if (ldb <= 4)
-        hipLaunchKernelGGL(k_batch<4>, grid, block, 0, st, tabs, dims, B, Rmax, ldb, max_pivots,
-                           out, rc, xv, snaps, status, npivots);
-    else if (ldb <= 8)
-        hipLaunchKernelGGL(k_batch<8>, grid, block, 0, st, tabs, dims, B, Rmax, ldb, max_pivots,
-                           out, rc, xv, snaps, status, npivots);
-    else if (ldb <= 16)
-        hipLaunchKernelGGL(k_batch<16>, grid, block, 0, st, tabs, dims, B, Rmax, ldb, max_pivots,
-                           out, rc, xv, snaps, status, npivots);
-    else if (ldb <= 32)
-        hipLaunchKernelGGL(k_batch<32>, grid, block, 0, st, tabs, dims, B, Rmax, ldb, max_pivots,
-                           out, rc, xv, snaps, status, npivots);
-    else
-        hipLaunchKernelGGL(k_batch<64>, grid, block, 0, st, tabs, dims, B, Rmax, ldb, max_pivots,
-                           out, rc, xv, snaps, status, npivots);
+    // k_batch<CMAX>: the smallest instantiation whose CMAX holds ldb
+    using BatchFn = void (*)(const double*, const int32_t*, int, int, int, int, double*, int32_t*,
+                             double*, double*, int32_t*, int32_t*);
+    const BatchFn fn = ldb <= 4 ? k_batch<4> : ldb <= 8 ? k_batch<8> : ldb <= 16 ? k_batch<16>
+                       : ldb <= 32 ? k_batch<32> : k_batch<64>;
+    hipLaunchKernelGGL(fn, dim3((B + 3) / 4), dim3(256), 0, S(stream), tabs, dims, B, Rmax, ldb,
+                       max_pivots, out, rc, xv, snaps, status, npivots);
     return (int)hipGetLastError();
 }
 
@@ -1449,28 +1453,37 @@ int shard_pivot(double* tin, double* tout, const smx_shape& s, int p, smx_ctl* c
     if (e1) (void)hipEventRecord(e1, st);
     return err;
 }
+
+// k pivots of the row-sharded chain in the mode of smx_tune_fused (k = 0 enqueues nothing).
+// ev (optional): 2 events per step recorded around its update launch.
+int launch_shard_chain(double* buf0, double* buf1, const smx_shape& s, int parity, int k,
+                       smx_ctl* ctl, smx_part* parts, double* send, double* recv, int nranks,
+                       ncclComm_t comm, int32_t* log, int64_t log_cap, hipEvent_t* ev,
+                       hipStream_t st) {
+    if (g_fused >= 2 && k > 0)
+        return shard_chain_overlap(buf0, buf1, s, parity, k, ctl, parts, send, recv, nranks, comm,
+                                   log, log_cap, ev, st, g_fused == 3);
+    if (g_fused && k > 0)
+        return shard_chain_fused(buf0, buf1, s, parity, k, ctl, parts, send, recv, nranks, comm,
+                                 log, log_cap, ev, st);
+    int err = 0;
+    for (int step = 0; step < k && !err; ++step) {
+        const int p = (parity + step) & 1;
+        err = shard_pivot(p ? buf1 : buf0, p ? buf0 : buf1, s, p, ctl, parts, send, recv, nranks,
+                          comm, log, log_cap, ev ? ev[2 * step] : nullptr,
+                          ev ? ev[2 * step + 1] : nullptr, st);
+    }
+    return err;
+}
 }  // namespace
 
 int smx_shard_run(double* buf0, double* buf1, const smx_shape* shape, int32_t parity, int32_t k,
                   smx_ctl* ctl, smx_part* parts, double* send, double* recv, int32_t nranks,
                   void* comm, int32_t* log, int64_t log_cap, void* stream) {
     if (!shape_ok(shape) || !comm || nranks < 1 || k < 0) return (int)hipErrorInvalidValue;
-    if (g_fused >= 2 && k > 0)
-        return shard_chain_overlap(buf0, buf1, *shape, parity & 1, k, ctl, parts, send, recv,
-                                   nranks, reinterpret_cast<ncclComm_t>(comm), log, log_cap,
-                                   nullptr, S(stream), g_fused == 3);
-    if (g_fused && k > 0)
-        return shard_chain_fused(buf0, buf1, *shape, parity & 1, k, ctl, parts, send, recv,
-                                 nranks, reinterpret_cast<ncclComm_t>(comm), log, log_cap,
-                                 nullptr, S(stream));
-    for (int step = 0; step < k; ++step) {
-        const int p = (parity + step) & 1;
-        const int err = shard_pivot(p ? buf1 : buf0, p ? buf0 : buf1, *shape, p, ctl, parts,
-                                    send, recv, nranks, reinterpret_cast<ncclComm_t>(comm), log,
-                                    log_cap, nullptr, nullptr, S(stream));
-        if (err) return err;
-    }
-    return 0;
+    return launch_shard_chain(buf0, buf1, *shape, parity & 1, k, ctl, parts, send, recv, nranks,
+                              reinterpret_cast<ncclComm_t>(comm), log, log_cap, nullptr,
+                              S(stream));
 }
 
 int smx_shard_run_timed(double* buf0, double* buf1, const smx_shape* shape, int32_t parity,
@@ -1479,31 +1492,11 @@ int smx_shard_run_timed(double* buf0, double* buf1, const smx_shape* shape, int3
                         float* host_update_ms, float* host_total_ms) {
     if (!shape_ok(shape) || !comm || nranks < 1 || k < 1 || !host_update_ms || !host_total_ms)
         return (int)hipErrorInvalidValue;
-    hipStream_t st = S(stream);
-    hipEvent_t* ev = nullptr;
-    if (timer_events((size_t)(2 * k + 1), &ev)) return (int)hipErrorOutOfMemory;
-    (void)hipEventRecord(ev[2 * k], st);
-    int err = 0;
-    if (g_fused >= 2)
-        err = shard_chain_overlap(buf0, buf1, *shape, parity & 1, k, ctl, parts, send, recv,
+    return run_timed(S(stream), k, false, host_update_ms, host_total_ms, [&](hipEvent_t* ev) {
+        return launch_shard_chain(buf0, buf1, *shape, parity & 1, k, ctl, parts, send, recv,
                                   nranks, reinterpret_cast<ncclComm_t>(comm), log, log_cap, ev,
-                                  st, g_fused == 3);
-    else if (g_fused)
-        err = shard_chain_fused(buf0, buf1, *shape, parity & 1, k, ctl, parts, send, recv,
-                                nranks, reinterpret_cast<ncclComm_t>(comm), log, log_cap, ev, st);
-    for (int step = 0; step < k && !err && !g_fused; ++step) {
-        const int p = (parity + step) & 1;
-        err = shard_pivot(p ? buf1 : buf0, p ? buf0 : buf1, *shape, p, ctl, parts, send, recv,
-                          nranks, reinterpret_cast<ncclComm_t>(comm), log, log_cap, ev[2 * step],
-                          ev[2 * step + 1], st);
-    }
-    if (!err) err = (int)hipEventSynchronize(ev[2 * k - 1]);
-    if (!err) {
-        for (int step = 0; step < k; ++step)
-            (void)hipEventElapsedTime(&host_update_ms[step], ev[2 * step], ev[2 * step + 1]);
-        (void)hipEventElapsedTime(host_total_ms, ev[2 * k], ev[2 * k - 1]);
-    }
-    return err;
+                                  S(stream));
+    });
 }
 
 int smx_shard_fused_prime(const double* T, const smx_shape* shape, int32_t parity, smx_ctl* ctl,
@@ -1722,22 +1715,11 @@ int64_t smx_block_bytes(const smx_shape* shape, int32_t* pivots_inout) {
 int smx_block_run(double* buf0, double* buf1, const smx_shape* shape, int32_t parity, int32_t k,
                   int32_t pivots, smx_ctl* ctl, void* blk, int64_t blk_bytes, int32_t* log,
                   double* xhist, int64_t log_cap, void* stream) {
-    if (!block_args_ok(shape, k, pivots, blk, blk_bytes) || buf0 == buf1 || !ctl)
+    if (!block_chain_ok(shape, k, pivots, blk, blk_bytes, buf0, buf1, ctl))
         return (int)hipErrorInvalidValue;
     if (k == 0) return 0;
     return launch_block_chain(buf0, buf1, *shape, parity & 1, k, pivots, ctl,
-                            static_cast<char*>(blk), log, xhist, log_cap, S(stream));
-}
-
-static int block_timed_read(int nb, float* host_sweep_ms, float* host_total_ms) {
-    hipEvent_t* ev = g_timer_ev;
-    int err = (int)hipEventSynchronize(ev[2 * nb + 1]);
-    if (!err) {
-        for (int b = 0; b < nb; ++b)
-            (void)hipEventElapsedTime(&host_sweep_ms[b], ev[2 * b], ev[2 * b + 1]);
-        (void)hipEventElapsedTime(host_total_ms, ev[2 * nb], ev[2 * nb + 1]);
-    }
-    return err;
+                              static_cast<char*>(blk), log, xhist, log_cap, S(stream));
 }
 
 int smx_block_run_timed(double* buf0, double* buf1, const smx_shape* shape, int32_t parity,
@@ -1746,61 +1728,37 @@ int smx_block_run_timed(double* buf0, double* buf1, const smx_shape* shape, int3
                         float* host_sweep_ms, float* host_total_ms) {
     // both outputs NULL: launch only (asynchronous); smx_block_timed_read waits and reads
     const bool defer = !host_sweep_ms && !host_total_ms;
-    if (!block_args_ok(shape, k, pivots, blk, blk_bytes) || buf0 == buf1 || !ctl || k < 1 ||
+    if (!block_chain_ok(shape, k, pivots, blk, blk_bytes, buf0, buf1, ctl) || k < 1 ||
         (!defer && (!host_sweep_ms || !host_total_ms)))
         return (int)hipErrorInvalidValue;
-    hipStream_t st = S(stream);
     const int nb = (k + pivots - 1) / pivots;
-    hipEvent_t* ev = nullptr;
-    if (timer_events((size_t)(2 * nb + 2), &ev)) return (int)hipErrorOutOfMemory;
-    (void)hipEventRecord(ev[2 * nb], st);
-    int err = launch_block_chain(buf0, buf1, *shape, parity & 1, k, pivots, ctl,
-                               static_cast<char*>(blk), log, xhist, log_cap, st, ev);
-    (void)hipEventRecord(ev[2 * nb + 1], st);
-    if (defer) {
-        if (!err) g_timed_blocks = nb;
-        return err;
-    }
-    return err ? err : block_timed_read(nb, host_sweep_ms, host_total_ms);
+    const int err = run_timed(S(stream), nb, true, host_sweep_ms, host_total_ms,
+                              [&](hipEvent_t* ev) {
+        return launch_block_chain(buf0, buf1, *shape, parity & 1, k, pivots, ctl,
+                                  static_cast<char*>(blk), log, xhist, log_cap, S(stream), ev);
+    });
+    if (defer && !err) g_timed_blocks = nb;
+    return err;
 }
 
 int smx_block_timed_read(int32_t blocks, float* host_sweep_ms, float* host_total_ms) {
     if (blocks < 1 || blocks != g_timed_blocks || !host_sweep_ms || !host_total_ms)
         return (int)hipErrorInvalidValue;
     g_timed_blocks = 0;
-    return block_timed_read(blocks, host_sweep_ms, host_total_ms);
+    return timed_read(blocks, true, host_sweep_ms, host_total_ms);
 }
 
 int smx_block_graph_create(double* buf0, double* buf1, const smx_shape* shape, int32_t parity,
                            int32_t k, int32_t pivots, smx_ctl* ctl, void* blk, int64_t blk_bytes,
                            int32_t* log, double* xhist, int64_t log_cap, void* stream,
                            void** graph_out) {
-    if (!block_args_ok(shape, k, pivots, blk, blk_bytes) || buf0 == buf1 || !ctl || k < 1 ||
+    if (!block_chain_ok(shape, k, pivots, blk, blk_bytes, buf0, buf1, ctl) || k < 1 ||
         !graph_out)
         return (int)hipErrorInvalidValue;
-    hipStream_t st = S(stream);
-    Graph* g = new Graph();
-    hipError_t err = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    if (err != hipSuccess) {
-        delete g;
-        return (int)err;
-    }
-    int lerr = launch_block_chain(buf0, buf1, *shape, parity & 1, k, pivots, ctl,
-                                static_cast<char*>(blk), log, xhist, log_cap, st);
-    err = hipStreamEndCapture(st, &g->graph);
-    if (lerr || err != hipSuccess) {
-        if (g->graph) (void)hipGraphDestroy(g->graph);
-        delete g;
-        return lerr ? lerr : (int)err;
-    }
-    err = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
-    if (err != hipSuccess) {
-        (void)hipGraphDestroy(g->graph);
-        delete g;
-        return (int)err;
-    }
-    *graph_out = g;
-    return 0;
+    return capture_graph(S(stream), graph_out, [&] {
+        return launch_block_chain(buf0, buf1, *shape, parity & 1, k, pivots, ctl,
+                                  static_cast<char*>(blk), log, xhist, log_cap, S(stream));
+    });
 }
 
 int64_t smx_bshard_bytes(const smx_shape* shape) {
@@ -1812,8 +1770,8 @@ int smx_bshard_run(double* buf0, double* buf1, const smx_shape* shape, int32_t p
                    int32_t pivots, smx_ctl* ctl, void* blk, int64_t blk_bytes, double* send,
                    double* recv, int32_t nranks, void* comm, int32_t* log, double* xhist,
                    int64_t log_cap, void* stream) {
-    if (!bshard_args_ok(shape, pivots, blk, blk_bytes) || buf0 == buf1 || !ctl || !send ||
-        !recv || nranks < 1 || !comm || k < 0)
+    if (!bshard_chain_ok(shape, k, pivots, blk, blk_bytes, buf0, buf1, ctl, send, recv, nranks,
+                         comm))
         return (int)hipErrorInvalidValue;
     if (k == 0) return 0;
     return launch_block_chain(buf0, buf1, *shape, parity & 1, k, pivots, ctl,
@@ -1830,33 +1788,14 @@ int smx_bshard_graph_create(double* buf0, double* buf1, const smx_shape* shape, 
                             int32_t k, int32_t pivots, smx_ctl* ctl, void* blk, int64_t blk_bytes,
                             double* send, double* recv, int32_t nranks, void* comm, int32_t* log,
                             double* xhist, int64_t log_cap, void* stream, void** graph_out) {
-    if (!bshard_args_ok(shape, pivots, blk, blk_bytes) || buf0 == buf1 || !ctl || !send ||
-        !recv || nranks < 1 || !comm || k < 1 || !graph_out)
+    if (!bshard_chain_ok(shape, k, pivots, blk, blk_bytes, buf0, buf1, ctl, send, recv, nranks,
+                         comm) || k < 1 || !graph_out)
         return (int)hipErrorInvalidValue;
-    hipStream_t st = S(stream);
-    Graph* g = new Graph();
-    hipError_t err = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    if (err != hipSuccess) {
-        delete g;
-        return (int)err;
-    }
-    int lerr = launch_block_chain(buf0, buf1, *shape, parity & 1, k, pivots, ctl,
-                                  static_cast<char*>(blk), log, xhist, log_cap, st, nullptr, send,
-                                  recv, nranks, reinterpret_cast<ncclComm_t>(comm));
-    err = hipStreamEndCapture(st, &g->graph);
-    if (lerr || err != hipSuccess) {
-        if (g->graph) (void)hipGraphDestroy(g->graph);
-        delete g;
-        return lerr ? lerr : (int)err;
-    }
-    err = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
-    if (err != hipSuccess) {
-        (void)hipGraphDestroy(g->graph);
-        delete g;
-        return (int)err;
-    }
-    *graph_out = g;
-    return 0;
+    return capture_graph(S(stream), graph_out, [&] {
+        return launch_block_chain(buf0, buf1, *shape, parity & 1, k, pivots, ctl,
+                                  static_cast<char*>(blk), log, xhist, log_cap, S(stream),
+                                  nullptr, send, recv, nranks, reinterpret_cast<ncclComm_t>(comm));
+    });
 }
 
 int smx_bshard_run_timed(double* buf0, double* buf1, const smx_shape* shape, int32_t parity,
@@ -1864,25 +1803,15 @@ int smx_bshard_run_timed(double* buf0, double* buf1, const smx_shape* shape, int
                          double* send, double* recv, int32_t nranks, void* comm, int32_t* log,
                          double* xhist, int64_t log_cap, void* stream, float* host_sweep_ms,
                          float* host_total_ms) {
-    if (!bshard_args_ok(shape, pivots, blk, blk_bytes) || buf0 == buf1 || !ctl || !send ||
-        !recv || nranks < 1 || !comm || k < 1 || !host_sweep_ms || !host_total_ms)
+    if (!bshard_chain_ok(shape, k, pivots, blk, blk_bytes, buf0, buf1, ctl, send, recv, nranks,
+                         comm) || k < 1 || !host_sweep_ms || !host_total_ms)
         return (int)hipErrorInvalidValue;
-    hipStream_t st = S(stream);
-    const int nb = (k + pivots - 1) / pivots;
-    hipEvent_t* ev = nullptr;
-    if (timer_events((size_t)(2 * nb + 2), &ev)) return (int)hipErrorOutOfMemory;
-    (void)hipEventRecord(ev[2 * nb], st);
-    int err = launch_block_chain(buf0, buf1, *shape, parity & 1, k, pivots, ctl,
-                                 static_cast<char*>(blk), log, xhist, log_cap, st, ev, send,
-                                 recv, nranks, reinterpret_cast<ncclComm_t>(comm));
-    (void)hipEventRecord(ev[2 * nb + 1], st);
-    if (!err) err = (int)hipEventSynchronize(ev[2 * nb + 1]);
-    if (!err) {
-        for (int b = 0; b < nb; ++b)
-            (void)hipEventElapsedTime(&host_sweep_ms[b], ev[2 * b], ev[2 * b + 1]);
-        (void)hipEventElapsedTime(host_total_ms, ev[2 * nb], ev[2 * nb + 1]);
-    }
-    return err;
+    return run_timed(S(stream), (k + pivots - 1) / pivots, true, host_sweep_ms, host_total_ms,
+                     [&](hipEvent_t* ev) {
+        return launch_block_chain(buf0, buf1, *shape, parity & 1, k, pivots, ctl,
+                                  static_cast<char*>(blk), log, xhist, log_cap, S(stream), ev,
+                                  send, recv, nranks, reinterpret_cast<ncclComm_t>(comm));
+    });
 }
 
 int smx_bshard_prime(const double* T, const smx_shape* shape, int32_t parity, smx_ctl* ctl,
@@ -2246,7 +2175,6 @@ int smx_mshard_graph_create(const smx_rank* ranks, int32_t nranks, int32_t parit
     int err = (int)hipSetDevice(ranks[0].device);
     for (int q = 0; q < nev && !err; ++q)
         err = (int)hipEventCreateWithFlags(&ev[(size_t)q], hipEventDisableTiming);
-    Graph* g = new Graph();
     if (!err) err = (int)hipStreamBeginCapture(st0, hipStreamCaptureModeThreadLocal);
     if (!err) {
         int lerr = (int)hipEventRecord(ev[0], st0);   // fork: every rank's stream joins
@@ -2260,21 +2188,12 @@ int smx_mshard_graph_create(const smx_rank* ranks, int32_t nranks, int32_t parit
             if (!lerr) lerr = (int)hipStreamWaitEvent(st0, ev[(size_t)q], 0);
         }
         (void)hipSetDevice(ranks[0].device);
-        const hipError_t e2 = hipStreamEndCapture(st0, &g->graph);
-        err = lerr ? lerr : (int)e2;
+        err = end_capture(st0, lerr, graph_out);
     }
-    if (!err) err = (int)hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
     for (hipEvent_t e : ev)
         if (e) (void)hipEventDestroy(e);
     (void)hipSetDevice(dev0);
-    if (err) {
-        if (g->exec) (void)hipGraphExecDestroy(g->exec);
-        if (g->graph) (void)hipGraphDestroy(g->graph);
-        delete g;
-        return err;
-    }
-    *graph_out = g;
-    return 0;
+    return err;
 }
 
 int smx_int_first_fix(const double* T0, double* T1, int64_t ld, int32_t rows, int32_t cols,

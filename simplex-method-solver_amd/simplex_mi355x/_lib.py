@@ -365,3 +365,16 @@ def check(err: int, what: str) -> None:
         code = -1000 - err
         raise RuntimeError(f"{what} failed: RCCL {NCCL_RESULTS.get(code, code)}")
     raise RuntimeError(f"{what} failed with hipError {err}")
+
+
+def call(name: str, *args) -> None:
+    """Call the library's ``name`` and raise on an error (:func:`check`)."""
+    check(getattr(load(), name)(*args), name)
+
+
+def call_timed(name: str, n: int, *args):
+    """:func:`call` for an entry point whose last two arguments are the outputs of a timed chain
+    (``n`` event-pair times and the total, float ms); returns them as (float32 array, float)."""
+    pairs, total = (ctypes.c_float * n)(), ctypes.c_float()
+    call(name, *args, pairs, ctypes.byref(total))
+    return np.frombuffer(pairs, dtype=np.float32).copy(), float(total.value)

@@ -28,6 +28,8 @@ reads the control block.
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -46,6 +48,14 @@ class Graph:
 
     def __init__(self, handle: int):
         self.handle = handle
+
+    @classmethod
+    def capture(cls, name: str, *args) -> "Graph":
+        """The graph made by the library's ``name`` (a ``*_graph_create``: ``args``, then the
+        handle output)."""
+        h = ctypes.c_void_p()
+        _lib.call(name, *args, ctypes.byref(h))
+        return cls(h.value)
 
     def launch(self, stream: int) -> None:
         _lib.check(_lib.load().smx_graph_launch(self.handle, stream), "smx_graph_launch")
@@ -250,18 +260,12 @@ class DeviceTableau:
             elif bplan is not None:
                 blk = self._blk_for(bplan)
                 if graph:
-                    g = self._graphs.get((p, k, "blk", bplan[1]))
-                    if g is None:
-                        g = self._make_block_graph(p, k, bplan[1])
-                    g.launch(self.stream.cuda_stream)
+                    self._graph(p, k, bplan[1]).launch(self.stream.cuda_stream)
                 else:
                     ops.block_run(self.buf, self.ctl, blk, self.log, self.xhist, self.shape, p,
                                   k, bplan[1])
             elif graph:
-                g = self._graphs.get((p, k))
-                if g is None:
-                    g = self._make_graph(p, k)
-                g.launch(self.stream.cuda_stream)
+                self._graph(p, k).launch(self.stream.cuda_stream)
             else:
                 ops.run(self.buf, self.ctl, self.parts, self.log, self.xhist, self.shape, p, k)
         # optimistic: if the chain stops early every later kernel is a no-op, and sync_state()
@@ -290,19 +294,42 @@ class DeviceTableau:
                 self._blk = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=self.device)
         return self._blk
 
-    def _make_block_graph(self, parity: int, k: int, pivots: int) -> Graph:
-        import ctypes
-        h = ctypes.c_void_p()
-        sh = ops.make_shape(self.shape)
+    def _chain_args(self, parity: int, k: int) -> tuple:
+        """The one-pivot chain's arguments (smx_run_timed, smx_graph_create) up to the stream;
+        the tuple keeps the ctypes shape it points to alive."""
+        return (self.buf[0].data_ptr(), self.buf[1].data_ptr(),
+                ctypes.byref(ops.make_shape(self.shape)), parity, k, self.ctl.data_ptr(),
+                self.parts.data_ptr(), self.log.data_ptr(), self.xhist.data_ptr(), self.log_cap,
+                self.stream.cuda_stream)
+
+    def _block_args(self, parity: int, k: int, pivots: int) -> tuple:
+        """The same for the block chain (smx_block_run_timed, smx_block_graph_create), with the
+        scratch of :meth:`_blk_for`."""
         blk = self._blk
-        _lib.check(_lib.load().smx_block_graph_create(
-            self.buf[0].data_ptr(), self.buf[1].data_ptr(), ctypes.byref(sh), parity, k, pivots,
-            self.ctl.data_ptr(), blk.data_ptr(), blk.numel() * 8, self.log.data_ptr(),
-            self.xhist.data_ptr(), self.log_cap, self.stream.cuda_stream, ctypes.byref(h)),
-            "smx_block_graph_create")
-        g = Graph(h.value)
-        self._graphs[(parity, k, "blk", pivots)] = g
+        return (self.buf[0].data_ptr(), self.buf[1].data_ptr(),
+                ctypes.byref(ops.make_shape(self.shape)), parity, k, pivots, self.ctl.data_ptr(),
+                blk.data_ptr(), blk.numel() * 8, self.log.data_ptr(), self.xhist.data_ptr(),
+                self.log_cap, self.stream.cuda_stream)
+
+    def _graph(self, parity: int, k: int, pivots: int | None = None) -> Graph:
+        """The captured chain of k pivots from ``parity`` (block pivots, ``pivots`` per sweep,
+        when given), captured on first use."""
+        key = (parity, k) if pivots is None else (parity, k, "blk", pivots)
+        g = self._graphs.get(key)
+        if g is None:
+            if pivots is None:
+                g = Graph.capture("smx_graph_create", *self._chain_args(parity, k))
+            else:
+                g = Graph.capture("smx_block_graph_create", *self._block_args(parity, k, pivots))
+            self._graphs[key] = g
         return g
+
+    def _timed_start(self) -> int:
+        """Settle the host state before a timed chain; returns the parity it starts on."""
+        self.settle()
+        if self._term:
+            self.clear_term()
+        return self.step & 1
 
     def block_timed_launcher(self, k: int, pivots: int):
         """``run_block_timed`` in two calls: the host preparation (shape, plan, scratch) is done
@@ -310,34 +337,23 @@ class DeviceTableau:
         (smx_block_run_timed with NULL outputs); ``read()`` waits for the chain's last event and
         returns (per-sweep ms array, device ms of the whole chain).  A timed region can bracket
         launch() and its own synchronize, with the event readout after it."""
-        import ctypes
-        self.settle()
-        if self._term:
-            self.clear_term()
-        p = self.step & 1
+        p = self._timed_start()
         nb = -(-k // pivots)
         plan = _lib.block_plan(self.shape, pivots)
         if plan is None:
             raise ValueError(f"shape {self.shape} is not eligible for block pivots")
-        blk = self._blk_for(plan)
-        sh = ops.make_shape(self.shape)
-        L = _lib.load()
-        args = (self.buf[0].data_ptr(), self.buf[1].data_ptr(), ctypes.byref(sh), p, k, pivots,
-                self.ctl.data_ptr(), blk.data_ptr(), blk.numel() * 8, self.log.data_ptr(),
-                self.xhist.data_ptr(), self.log_cap, self.stream.cuda_stream)
+        self._blk_for(plan)
+        run = _lib.load().smx_block_run_timed
+        args = self._block_args(p, k, pivots)   # (the closure keeps them, so the shape, alive)
 
         def launch() -> None:
-            _lib.check(L.smx_block_run_timed(*args, None, None), "smx_block_run_timed")
+            _lib.check(run(*args, None, None), "smx_block_run_timed")
             self.step += k
             self._pending = True
 
         def read():
-            sw = (ctypes.c_float * nb)()
-            tot = ctypes.c_float()
-            _lib.check(L.smx_block_timed_read(nb, sw, ctypes.byref(tot)), "smx_block_timed_read")
-            return np.frombuffer(sw, dtype=np.float32).copy(), float(tot.value)
+            return _lib.call_timed("smx_block_timed_read", nb, nb)
 
-        launch.shape = sh   # keeps the ctypes shape alive as long as the closures
         return launch, read
 
     def run_block_timed(self, k: int, pivots: int):
@@ -376,33 +392,16 @@ class DeviceTableau:
         bplan = self.block_plan()
         if bplan is not None:
             self._blk_for(bplan)
-            if (p, k, "blk", bplan[1]) not in self._graphs:
-                with torch.cuda.stream(self.stream):
-                    self._make_block_graph(p, k, bplan[1])
-            return
-        if (p, k) not in self._graphs:
-            with torch.cuda.stream(self.stream):
-                self._make_graph(p, k)
+        with torch.cuda.stream(self.stream):
+            self._graph(p, k, bplan[1] if bplan is not None else None)
 
     def run_timed(self, k: int):
         """k chained pivots with HIP events around every update kernel (synchronous).
         Returns (per-update-kernel ms array, device ms of the whole chain)."""
-        import ctypes
-        self.settle()
-        if self._term:
-            self.clear_term()
-        p = self.step & 1
-        upd = (ctypes.c_float * k)()
-        tot = ctypes.c_float()
-        sh = ops.make_shape(self.shape)
-        _lib.check(_lib.load().smx_run_timed(
-            self.buf[0].data_ptr(), self.buf[1].data_ptr(), ctypes.byref(sh), p, k,
-            self.ctl.data_ptr(), self.parts.data_ptr(), self.log.data_ptr(),
-            self.xhist.data_ptr(), self.log_cap, self.stream.cuda_stream, upd,
-            ctypes.byref(tot)), "smx_run_timed")
+        out = _lib.call_timed("smx_run_timed", k, *self._chain_args(self._timed_start(), k))
         self.step += k
         self._pending = True
-        return np.frombuffer(upd, dtype=np.float32).copy(), float(tot.value)
+        return out
 
     def sync_state(self) -> np.void:
         """Read the control block and set the host step counter to the device pivot count."""
@@ -437,20 +436,6 @@ class DeviceTableau:
         with torch.cuda.stream(self.stream):
             self.ctl.view(torch.int32)[4] = 0   # smx_ctl.term (byte offset 16)
         self._term = False
-
-    def _make_graph(self, parity: int, k: int) -> Graph:
-        import ctypes
-        h = ctypes.c_void_p()
-        sh = ops.make_shape(self.shape)
-        b0, b1 = self.buf[0].data_ptr(), self.buf[1].data_ptr()
-        _lib.check(_lib.load().smx_graph_create(
-            b0, b1, ctypes.byref(sh), parity, k, self.ctl.data_ptr(), self.parts.data_ptr(),
-            self.log.data_ptr(), self.xhist.data_ptr(), self.log_cap, self.stream.cuda_stream,
-            ctypes.byref(h)),
-            "smx_graph_create")
-        g = Graph(h.value)
-        self._graphs[(parity, k)] = g
-        return g
 
     def forced(self, r: int, c: int) -> None:
         """Forced pivot (no selection, no bookkeeping): buf[s&1] -> buf[(s+1)&1]."""

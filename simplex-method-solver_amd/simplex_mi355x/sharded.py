@@ -72,7 +72,25 @@ class RcclComm:
             self.handle = None
 
 
-class HipShardBackend:
+class _ShardState:
+    """What the protocol drivers read from either backend's DeviceTableau (``self.dev``)."""
+
+    def stream_ctx(self):
+        return torch.cuda.stream(self.dev.stream)
+
+    def state(self) -> dict:
+        c = self.dev.sync_state()
+        return {"npivots": int(c["npivots"]), "term": bool(c["term"]),
+                "status": int(c["sel_status"]), "r": int(c["sel_r"]), "c": int(c["sel_c"])}
+
+    def log(self, start: int, stop: int) -> np.ndarray:
+        return self.dev.read_log(start, stop)
+
+    def local_table(self) -> np.ndarray:
+        return self.dev.download()
+
+
+class HipShardBackend(_ShardState):
     """This rank's slice of the tableau in HBM plus the exchange buffers.
 
     ``fused`` (default: the library's chain mode, smx_tune_fused): a pivot is fused pack ->
@@ -102,9 +120,6 @@ class HipShardBackend:
         self.overlap = overlap if (overlap and self.fused) else False
         self._records = False   # look-ahead records of step dev.step are in dev.parts
         self._packed = False    # overlap form: send already holds step dev.step's pack
-
-    def stream_ctx(self):
-        return torch.cuda.stream(self.dev.stream)
 
     def begin(self) -> None:
         d = self.dev
@@ -173,61 +188,37 @@ class HipShardBackend:
         d.step += 1
         d._pending = True
 
-    def _chain_mode(self):
-        """Run the native chain in this backend's mode (smx_tune_fused is process-wide)."""
+    @contextlib.contextmanager
+    def _native_chain(self, k: int, comm: "RcclComm"):
+        """The arguments of smx_shard_run* up to the stream, with the library in this backend's
+        chain mode meanwhile (smx_tune_fused is process-wide); k pivots are booked on leaving."""
+        d = self.dev
         L = _lib.load()
         mode = (3 if self.overlap == "values" else 2) if self.overlap else 1
         prev = L.smx_tune_fused(mode if self.fused else 0)
-        return L, prev
-
-    def run_native(self, k: int, comm: "RcclComm") -> None:
-        """k pivots, all-gathers issued by libsmx.so on the solver stream (no host sync)."""
-        d = self.dev
-        L, prev = self._chain_mode()
         try:
-            _lib.check(L.smx_shard_run(
-                d.buf[0].data_ptr(), d.buf[1].data_ptr(), ctypes.byref(self._shape), d.step & 1,
-                k, d.ctl.data_ptr(), d.parts.data_ptr(), self.send.data_ptr(),
-                self._recv2.data_ptr(), self.world, comm.handle, d.log.data_ptr(), d.log_cap,
-                d.stream.cuda_stream), "smx_shard_run")
+            yield (d.buf[0].data_ptr(), d.buf[1].data_ptr(), ctypes.byref(self._shape),
+                   d.step & 1, k, d.ctl.data_ptr(), d.parts.data_ptr(), self.send.data_ptr(),
+                   self._recv2.data_ptr(), self.world, comm.handle, d.log.data_ptr(), d.log_cap,
+                   d.stream.cuda_stream)
         finally:
             L.smx_tune_fused(prev)
         d.step += k
         d._pending = True
         self._records = self._packed = False   # the native chain may keep fewer records
 
+    def run_native(self, k: int, comm: "RcclComm") -> None:
+        """k pivots, all-gathers issued by libsmx.so on the solver stream (no host sync)."""
+        with self._native_chain(k, comm) as args:
+            _lib.call("smx_shard_run", *args)
+
     def run_native_timed(self, k: int, comm: "RcclComm"):
         """Like run_native, with HIP events around every update kernel (synchronous)."""
-        d = self.dev
-        upd = (ctypes.c_float * k)()
-        tot = ctypes.c_float()
-        L, prev = self._chain_mode()
-        try:
-            _lib.check(L.smx_shard_run_timed(
-                d.buf[0].data_ptr(), d.buf[1].data_ptr(), ctypes.byref(self._shape), d.step & 1,
-                k, d.ctl.data_ptr(), d.parts.data_ptr(), self.send.data_ptr(),
-                self._recv2.data_ptr(), self.world, comm.handle, d.log.data_ptr(), d.log_cap,
-                d.stream.cuda_stream, upd, ctypes.byref(tot)), "smx_shard_run_timed")
-        finally:
-            L.smx_tune_fused(prev)
-        d.step += k
-        d._pending = True
-        self._records = self._packed = False
-        return np.frombuffer(upd, dtype=np.float32).copy(), float(tot.value)
-
-    def state(self) -> dict:
-        c = self.dev.sync_state()
-        return {"npivots": int(c["npivots"]), "term": bool(c["term"]),
-                "status": int(c["sel_status"]), "r": int(c["sel_r"]), "c": int(c["sel_c"])}
-
-    def log(self, start: int, stop: int) -> np.ndarray:
-        return self.dev.read_log(start, stop)
-
-    def local_table(self) -> np.ndarray:
-        return self.dev.download()
+        with self._native_chain(k, comm) as args:
+            return _lib.call_timed("smx_shard_run_timed", k, *args)
 
 
-class BlockShardBackend:
+class BlockShardBackend(_ShardState):
     """This rank's row block for BLOCK pivots (smx_bshard_*, csrc/smx_block.hpp): per pivot the
     rank packs its header + candidate rows as values of T_{k+D} derived from the block's input,
     one all-gather exchanges the slots (the layout of the one-pivot protocol above), and the step
@@ -252,9 +243,7 @@ class BlockShardBackend:
                                     device=self.dev.device)
             self.blk = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=self.dev.device)
         self._nbytes = nbytes
-
-    def stream_ctx(self):
-        return torch.cuda.stream(self.dev.stream)
+        self._graphs: dict[tuple, Graph] = {}
 
     # -- the step-wise protocol (include/smx.h, smx_bshard_*) ---------------------------------
     def parity(self) -> int:
@@ -313,8 +302,7 @@ class BlockShardBackend:
         _lib.check(_lib.load().smx_bshard_sweep(
             d.buf[parity].data_ptr(), d.buf[parity ^ 1].data_ptr(), ctypes.byref(self._shape),
             pivots, self.blk.data_ptr(), self._nbytes, d.stream.cuda_stream), "smx_bshard_sweep")
-        d.step += pivots
-        d._pending = True
+        self._ran(pivots)
 
     def publish(self, parity: int, block: int) -> None:
         d = self.dev
@@ -323,46 +311,42 @@ class BlockShardBackend:
             self._nbytes, d.stream.cuda_stream), "smx_bshard_publish")
 
     # -- the native chain (libsmx issues the all-gathers) -------------------------------------
-    def run_native(self, k: int, comm: "RcclComm") -> None:
+    def _chain_args(self, k: int, comm: "RcclComm") -> tuple:
+        """The arguments of smx_bshard_run / _run_timed / _graph_create up to the stream."""
         d = self.dev
-        _lib.check(_lib.load().smx_bshard_run(
-            d.buf[0].data_ptr(), d.buf[1].data_ptr(), ctypes.byref(self._shape), d.step & 1, k,
-            self.pivots, d.ctl.data_ptr(), self.blk.data_ptr(), self._nbytes,
-            self.send.data_ptr(), self.recv.data_ptr(), self.world, comm.handle,
-            d.log.data_ptr(), d.xhist.data_ptr(), d.log_cap, d.stream.cuda_stream),
-            "smx_bshard_run")
-        d.step += k
-        d._pending = True
+        return (d.buf[0].data_ptr(), d.buf[1].data_ptr(), ctypes.byref(self._shape), d.step & 1,
+                k, self.pivots, d.ctl.data_ptr(), self.blk.data_ptr(), self._nbytes,
+                self.send.data_ptr(), self.recv.data_ptr(), self.world, comm.handle,
+                d.log.data_ptr(), d.xhist.data_ptr(), d.log_cap, d.stream.cuda_stream)
+
+    def _ran(self, k: int) -> None:
+        self.dev.step += k
+        self.dev._pending = True
+
+    def run_native(self, k: int, comm: "RcclComm") -> None:
+        _lib.call("smx_bshard_run", *self._chain_args(k, comm))
+        self._ran(k)
 
     def graph(self, k: int, comm: "RcclComm") -> Graph:
         """run_native's chain of k pivots captured as a hipGraph (smx_bshard_graph_create), for
         the current parity; cached per (parity, k, comm)."""
-        d = self.dev
         # the exchange form is baked in at capture time, and a communicator handle can be reused
         # after close: key on both (close() / drop_graphs() free the cache)
-        key = (d.step & 1, int(k), id(comm), comm.handle, _lib.tune_shard_xchg(-2))
-        graphs = self.__dict__.setdefault("_graphs", {})
-        if key not in graphs:
-            h = ctypes.c_void_p()
-            _lib.check(_lib.load().smx_bshard_graph_create(
-                d.buf[0].data_ptr(), d.buf[1].data_ptr(), ctypes.byref(self._shape), d.step & 1,
-                k, self.pivots, d.ctl.data_ptr(), self.blk.data_ptr(), self._nbytes,
-                self.send.data_ptr(), self.recv.data_ptr(), self.world, comm.handle,
-                d.log.data_ptr(), d.xhist.data_ptr(), d.log_cap, d.stream.cuda_stream,
-                ctypes.byref(h)), "smx_bshard_graph_create")
-            graphs[key] = Graph(h.value)
-        return graphs[key]
+        key = (self.dev.step & 1, int(k), id(comm), comm.handle, _lib.tune_shard_xchg(-2))
+        if key not in self._graphs:
+            self._graphs[key] = Graph.capture("smx_bshard_graph_create",
+                                              *self._chain_args(k, comm))
+        return self._graphs[key]
 
     def run_graph(self, k: int, comm: "RcclComm") -> None:
         """run_native(k, comm) as one replay of the captured chain (one host call)."""
-        g = self.graph(k, comm)
-        g.launch(self.dev.stream.cuda_stream)
-        self.dev.step += k
-        self.dev._pending = True
+        self.graph(k, comm).launch(self.dev.stream.cuda_stream)
+        self._ran(k)
 
     def drop_graphs(self) -> None:
-        for g in self.__dict__.pop("_graphs", {}).values():
+        for g in self._graphs.values():
             g.destroy()
+        self._graphs.clear()
 
     def close(self) -> None:
         """Free the captured chains (they hold the communicator they were captured with)."""
@@ -370,31 +354,10 @@ class BlockShardBackend:
 
     def run_native_timed(self, k: int, comm: "RcclComm"):
         """Like run_native, with HIP events around every sweep (synchronous)."""
-        d = self.dev
-        nb = -(-k // self.pivots)
-        sw = (ctypes.c_float * nb)()
-        tot = ctypes.c_float()
-        _lib.check(_lib.load().smx_bshard_run_timed(
-            d.buf[0].data_ptr(), d.buf[1].data_ptr(), ctypes.byref(self._shape), d.step & 1, k,
-            self.pivots, d.ctl.data_ptr(), self.blk.data_ptr(), self._nbytes,
-            self.send.data_ptr(), self.recv.data_ptr(), self.world, comm.handle,
-            d.log.data_ptr(), d.xhist.data_ptr(), d.log_cap, d.stream.cuda_stream, sw,
-            ctypes.byref(tot)),
-            "smx_bshard_run_timed")
-        d.step += k
-        d._pending = True
-        return np.frombuffer(sw, dtype=np.float32).copy(), float(tot.value)
-
-    def state(self) -> dict:
-        c = self.dev.sync_state()
-        return {"npivots": int(c["npivots"]), "term": bool(c["term"]),
-                "status": int(c["sel_status"]), "r": int(c["sel_r"]), "c": int(c["sel_c"])}
-
-    def log(self, start: int, stop: int) -> np.ndarray:
-        return self.dev.read_log(start, stop)
-
-    def local_table(self) -> np.ndarray:
-        return self.dev.download()
+        out = _lib.call_timed("smx_bshard_run_timed", -(-k // self.pivots),
+                              *self._chain_args(k, comm))
+        self._ran(k)
+        return out
 
 
 def rank_block_pivots(rows: int, m: int) -> int:
@@ -704,8 +667,3 @@ def bench_main(args, metric, peak_gbs, cpu_baseline_fn=None, load_traffic=None,
         be.close()   # captured chains reference comm: free them before it
     comm.close()
     dist.destroy_process_group()
-
-
-@contextlib.contextmanager
-def _null():
-    yield
