@@ -218,6 +218,35 @@ int smx_batch_gm_fits(int32_t Rmax, int32_t ldb);
  * depend on any of them.  Defaults (the measured winners): 1024, 0, 8. */
 int smx_tune_batch_gm(int32_t block, int32_t mirrors, int32_t unroll);
 
+/* ---- a batch's solutions on the device (one wavefront per LP) ------------------------------
+ * After smx_batch_solve, smx_batch_solve_wg or smx_batch_solve_gm: turns every problem's final
+ * table (final = their out, fp64 [B][Rmax][ldb]) and pivot log (rc, npivots; max_pivots as in the
+ * solve) into its solution, so that a caller copies back the answer and not the tables.  Labels
+ * are int32 codes: k in 0..m-1 is 'x{k+1}', m + i with 0 <= i < n is 'y{i+1}'; basis[i] (the
+ * label of constraint row i) starts as m + i, nonbasis[j] (the label of column j) as j, and a
+ * logged pivot (r, c) swaps basis[r] with nonbasis[c] (simplex.py:152; an entry outside r < n,
+ * c < m is skipped).  func = fp64 [B][ldb], the ORIGINAL objective row of every problem (row n_b
+ * of tabs); only its first m_b entries are read.  Outputs, whatever the problem's status:
+ *   x         fp64 [B][ldb]    x[k] = T[i][m] where basis[i] == k, else +0.0; +0.0 at k >= m_b
+ *   duals     fp64 [B][Rmax]   duals[i] = T[n][j] where nonbasis[j] == m + i (the f-row entry
+ *                              under 'y{i+1}', in the tableau's sign), else +0.0; +0.0 at i >= n_b
+ *   objective fp64 [B]         func[0]*x[0] + func[1]*x[1] + ... + func[m-1]*x[m-1]: every
+ *                              product rounded on its own, summed strictly left to right starting
+ *                              from the first product, no FMA (for m = 2 the reference's optimum)
+ *   basis     int32 [B][Rmax], nonbasis int32 [B][ldb]; -1 at i >= n_b, j >= m_b
+ * A problem without 1 <= n_b < Rmax and 1 <= m_b < ldb gets the padding values only and objective
+ * +0.0.  Returns hipErrorInvalidValue (1) before any HIP call for B < 0, max_pivots < 0, a shape
+ * outside smx_batch_solution_lds_bytes or, with B > 0, a null pointer; B == 0 returns 0 without
+ * a launch. */
+int smx_batch_solution(const double* final, const int32_t* dims, int32_t B, int32_t Rmax,
+                       int32_t ldb, int32_t max_pivots, const int32_t* rc,
+                       const int32_t* npivots, const double* func, double* x, double* duals,
+                       double* objective, int32_t* basis, int32_t* nonbasis, void* stream);
+/* Host only: the dynamic LDS (bytes) one block of smx_batch_solution needs, 16 * (Rmax + ldb), or
+ * -1 for Rmax < 2, ldb < 2 or Rmax + ldb > 8192 (128 KiB; the sum bound of smx_batch_gm_fits, so
+ * every shape a batch kernel takes is inside).  The single statement of that envelope. */
+int64_t smx_batch_solution_lds_bytes(int32_t Rmax, int32_t ldb);
+
 /* ---- row-sharded engine (one process per GPU; exchange = caller's all-gather) ----------
  * Local tableau: shape->rows constraint rows (global rows row0 .. row0+rows-1) + a replica
  * of the f-row as local row `rows`.  Per pivot:

@@ -11,6 +11,8 @@
 //   smx_batch_wg.hpp  wg_pivot_loop (the get_solution loop of one workgroup on one LP) and
 //                     k_batch_wg (one mid-sized LP per workgroup, tableau in LDS)
 //   smx_batch_gm.hpp  k_batch_gm (one LP past the LDS edge per workgroup, tableau in global memory)
+//   smx_solution.hpp  k_batch_solution (a batch's final tables and pivot logs -> x, duals,
+//                     objective and labels, one wavefront per LP)
 //   smx_resident.hpp  k_resident: the whole pivot loop in one persistent launch, tableau in LDS
 //   smx_block.hpp     k_blk_*: P pivots per HBM sweep, decisions planned from the sweep's input
 // and this file holds the host side: grid sizing, variants, chains, graphs, RCCL, the C ABI.
@@ -56,6 +58,7 @@ static_assert(sizeof(smx_part) == 32, "smx_part layout");
 #include "smx_batch.hpp"
 #include "smx_batch_wg.hpp"
 #include "smx_batch_gm.hpp"
+#include "smx_solution.hpp"
 #include "smx_resident.hpp"
 #include "smx_block.hpp"
 #include "smx_window.hpp"
@@ -1237,6 +1240,42 @@ int smx_batch_solve_gm(const double* tabs, const int32_t* dims, int32_t B, int32
                   xv, snaps, status, npivots, S(stream));
 }
 
+
+// ---- a batch's solutions from its final tables and pivot logs (smx_solution.hpp) --------------
+// The envelope: four waves' label arrays and inverse maps, 16 * (Rmax + ldb) bytes, within
+// 128 KiB -- the sum bound of gm_fits, so every shape any batch kernel takes is inside it.
+namespace {
+
+constexpr int64_t kSolMaxSum = 8192;
+
+inline int64_t sol_lds_bytes(int64_t Rmax, int64_t ldb) {
+    if (Rmax < 2 || ldb < 2 || Rmax + ldb > kSolMaxSum) return -1;
+    return 4 * kSolWaves * (Rmax + ldb);
+}
+
+}  // namespace
+
+int64_t smx_batch_solution_lds_bytes(int32_t Rmax, int32_t ldb) {
+    return sol_lds_bytes(Rmax, ldb);
+}
+
+int smx_batch_solution(const double* final, const int32_t* dims, int32_t B, int32_t Rmax,
+                       int32_t ldb, int32_t max_pivots, const int32_t* rc,
+                       const int32_t* npivots, const double* func, double* x, double* duals,
+                       double* objective, int32_t* basis, int32_t* nonbasis, void* stream) {
+    const int64_t lds = sol_lds_bytes(Rmax, ldb);
+    if (!wg_args_ok(B, max_pivots) || lds < 0) return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    if (!final || !dims || !rc || !npivots || !func || !x || !duals || !objective || !basis ||
+        !nonbasis)
+        return (int)hipErrorInvalidValue;
+    if (const int err = wg_raise_lds_limit<k_batch_solution>((int)(4 * kSolWaves * kSolMaxSum)))
+        return err;
+    hipLaunchKernelGGL(k_batch_solution, dim3((B + kSolWaves - 1) / kSolWaves),
+                       dim3(kSolWaves * kWave), (size_t)lds, S(stream), final, dims, B, Rmax, ldb,
+                       max_pivots, rc, npivots, func, x, duals, objective, basis, nonbasis);
+    return (int)hipGetLastError();
+}
 
 // ---- native RCCL shard driver: the all-gather on the solver's own stream --------------------
 // (torch.distributed would run it on its own NCCL stream: one cross-stream event wait per pivot,

@@ -14,6 +14,11 @@ past the LDS edge, up to a 724 x 724 table, run one workgroup each with the tabl
 ``GM_MIN_BATCH`` of them.  Problems outside all three envelopes (bigger, ragged, int entries, or
 with a ``len(function)`` the reference would index out of range) go through ``SimplexMethod``
 one by one -- still on the device.
+
+``solve_batch_solutions`` (and ``solve_batch_arrays(solution=True)``) answer with every LP's whole
+solution -- all of x, the duals, the objective, the labels -- formed on the device by
+``k_batch_solution`` (csrc/smx_solution.hpp) from the final tables and pivot logs; with
+``tables=False`` only that comes back, not the tables.
 """
 from __future__ import annotations
 
@@ -23,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import MESSAGES, Error, Info, SimplexMethod
+from .engine import MESSAGES, Error, Info, SimplexMethod, Solution
 
 # The wave kernel's envelope (k_batch): past it a launch goes to the workgroup kernel
 # (k_batch_wg), whose own envelope -- what one CU's LDS holds -- only the library states
@@ -61,6 +66,14 @@ def gm_fits(Rmax: int, ldb: int) -> bool:
     if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
         return False
     return bool(_lib.load().smx_batch_gm_fits(int(Rmax), int(ldb)))
+
+
+def solution_lds_bytes(Rmax: int, ldb: int) -> int:
+    """Dynamic LDS one block of k_batch_solution needs for a launch of Rmax x ldb blocks, -1 when
+    the shape is outside that kernel's envelope (the library is the one source of the rule)."""
+    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
+        return -1
+    return int(_lib.load().smx_batch_solution_lds_bytes(int(Rmax), int(ldb)))
 
 
 def _shape(cons, func):
@@ -158,7 +171,8 @@ def _fallback(cons, func, max_pivots, history):
 
 
 def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256,
-                       history: bool = False, device=None, kernel: str = "auto") -> dict:
+                       history: bool = False, device=None, kernel: str = "auto",
+                       solution: bool = False, tables: bool = True) -> dict:
     """Array-level batch solve (no Python objects per problem).
 
     ``tabs``: float64 [B][Rmax][ldb], problem k in rows 0..n_k (f-row = row n_k), columns
@@ -174,7 +188,18 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
     ``xv`` [B][P][2] (x1, x2 after each pivot) and, with ``history``, ``snaps``
     [sum(npivots)][Rmax][ldb] -- problem k's tables after each of its pivots are
     ``snaps[snap_off[k]:snap_off[k + 1]]`` (compacted on the device before the copy back).
+
+    ``solution=True`` adds what ``k_batch_solution`` makes of every final table and pivot log on
+    the device (labels as int32 codes: k in 0..m-1 is 'x{k+1}', m + i is 'y{i+1}'): ``x``
+    [B][ldb - 1] (+0.0 past m_k), ``duals`` [B][Rmax - 1] (+0.0 past n_k), ``objective`` [B],
+    ``basis`` [B][Rmax - 1] and ``nonbasis`` [B][ldb - 1] (-1 past n_k / m_k); see ``Solution``.
+    ``tables=False`` (only with ``solution=True`` and without ``history``) leaves the final tables
+    on the device: the result has no ``final``.
     """
+    if not tables and not solution:
+        raise ValueError("tables=False needs solution=True: nothing else would report the answer")
+    if not tables and history:
+        raise ValueError("history=True needs the tables: tables=False cannot go with it")
     if not torch.cuda.is_available():
         raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
     tabs = np.ascontiguousarray(tabs, dtype=np.float64)
@@ -185,6 +210,8 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
     which = choose_kernel(Rmax, ldb, kernel) if B else "wave"
     if B and ((dims[:, 0] + 1 > Rmax).any() or (dims[:, 1] + 1 > ldb).any() or
               (dims[:, 1] < 1).any() or (dims[:, 0] < 1).any()):
+        raise ValueError(ENVELOPE_ERROR)
+    if solution and solution_lds_bytes(Rmax, ldb) < 0:
         raise ValueError(ENVELOPE_ERROR)
     P = int(max_pivots)
     L = _lib.load()
@@ -207,9 +234,27 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
             d_tabs.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, P, d_out.data_ptr(),
             d_rc.data_ptr(), d_xv.data_ptr(), d_snaps.data_ptr() if history else None,
             d_st.data_ptr(), d_np.data_ptr(), stream.cuda_stream), what)
-        res = {"final": d_out.cpu().numpy(), "rc": d_rc.cpu().numpy(),
-               "xv": d_xv.cpu().numpy(), "status": d_st.cpu().numpy(),
-               "npivots": d_np.cpu().numpy()}
+        res = {"final": d_out.cpu().numpy()} if tables else {}
+        res.update({"rc": d_rc.cpu().numpy(), "xv": d_xv.cpu().numpy(),
+                    "status": d_st.cpu().numpy(), "npivots": d_np.cpu().numpy()})
+        if solution:
+            # the original objective rows (row n_k of problem k), gathered on the device
+            d_func = d_tabs[torch.arange(B, device=dev), d_dims[:, 0].long()].contiguous()
+            d_x = torch.empty((B, ldb), dtype=torch.float64, device=dev)
+            d_du = torch.empty((B, Rmax), dtype=torch.float64, device=dev)
+            d_obj = torch.empty(B, dtype=torch.float64, device=dev)
+            d_ba = torch.empty((B, Rmax), dtype=torch.int32, device=dev)
+            d_nb = torch.empty((B, ldb), dtype=torch.int32, device=dev)
+            _lib.check(L.smx_batch_solution(
+                d_out.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, P, d_rc.data_ptr(),
+                d_np.data_ptr(), d_func.data_ptr(), d_x.data_ptr(), d_du.data_ptr(),
+                d_obj.data_ptr(), d_ba.data_ptr(), d_nb.data_ptr(), stream.cuda_stream),
+                "smx_batch_solution")
+            res.update({"x": d_x[:, :ldb - 1].contiguous().cpu().numpy(),
+                        "duals": d_du[:, :Rmax - 1].contiguous().cpu().numpy(),
+                        "objective": d_obj.cpu().numpy(),
+                        "basis": d_ba[:, :Rmax - 1].contiguous().cpu().numpy(),
+                        "nonbasis": d_nb[:, :ldb - 1].contiguous().cpu().numpy()})
         if history:
             steps = torch.arange(max(P, 1), device=dev)[None, :] < d_np[:, None]
             res["snaps"] = d_snaps[steps].cpu().numpy()
@@ -284,6 +329,36 @@ def gm_launches(shapes, max_pivots: int, history: bool):
                            lambda R, C: R * C if gm_fits(R, C) else -1, GM_TABLE_BUDGET)
 
 
+def _routes(problems, kernel):
+    """``route`` of every problem, then what ``kernel`` makes of it (``solve_batch``)."""
+    routes = [route(c, f) for c, f in problems]
+    if kernel == "wave" and "workgroup" in routes:
+        raise ValueError(ENVELOPE_ERROR)
+    if kernel == "workgroup":
+        routes = ["workgroup" if r == "wave" else r for r in routes]
+    if kernel == "global":
+        routes = [r if r == "single" else "global" for r in routes]
+    elif kernel != "auto" or routes.count("global") < GM_MIN_BATCH:
+        routes = ["single" if r == "global" else r for r in routes]
+    return routes
+
+
+def _launches(problems, routes, max_pivots, history):
+    """[(kernel, problem indices)]: the wave problems in one launch, the workgroup and global
+    problems in the launches of ``wg_launches`` / ``gm_launches``."""
+    launches = []
+    idx = [k for k, r in enumerate(routes) if r == "wave"]
+    if idx:
+        launches.append(("wave", idx))
+    for which, split in (("workgroup", wg_launches), ("global", gm_launches)):
+        idx = [k for k, r in enumerate(routes) if r == which]
+        if idx:
+            shapes = [(len(problems[k][0]), len(problems[k][0][0]) - 1) for k in idx]
+            launches += [(which, [idx[q] for q in part])
+                         for part in split(shapes, max_pivots, history)]
+    return launches
+
+
 def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=None,
                 kernel: str = "auto"):
     """Solve every ``(constraints, function)``; returns ``(results, statuses)``.
@@ -308,28 +383,11 @@ def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=No
         raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
     results = [None] * len(problems)
     statuses = [None] * len(problems)
-    routes = [route(c, f) for c, f in problems]
-    if kernel == "wave" and "workgroup" in routes:
-        raise ValueError(ENVELOPE_ERROR)
-    if kernel == "workgroup":
-        routes = ["workgroup" if r == "wave" else r for r in routes]
-    if kernel == "global":
-        routes = [r if r == "single" else "global" for r in routes]
-    elif kernel != "auto" or routes.count("global") < GM_MIN_BATCH:
-        routes = ["single" if r == "global" else r for r in routes]
+    routes = _routes(problems, kernel)
     for k, (c, f) in enumerate(problems):
         if routes[k] == "single":
             results[k], statuses[k] = _fallback(c, f, max_pivots, history)
-    launches = []                                            # (kernel, problem indices)
-    idx = [k for k, r in enumerate(routes) if r == "wave"]
-    if idx:
-        launches.append(("wave", idx))
-    for which, split in (("workgroup", wg_launches), ("global", gm_launches)):
-        idx = [k for k, r in enumerate(routes) if r == which]
-        if idx:
-            shapes = [(len(problems[k][0]), len(problems[k][0][0]) - 1) for k in idx]
-            launches += [(which, [idx[q] for q in part])
-                         for part in split(shapes, max_pivots, history)]
+    launches = _launches(problems, routes, max_pivots, history)
     P = int(max_pivots)
     for which, idx in launches:
         tabs, dims = pack([problems[k] for k in idx])
@@ -348,6 +406,59 @@ def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=No
         finally:
             if gc_was_on:
                 gc.enable()
+    return results, statuses
+
+
+def _fallback_solution(cons, func, max_pivots):
+    try:
+        sm = SimplexMethod(cons, func)
+        sm.solve(record_history=False, max_pivots=max_pivots)
+        return sm.solution(), sm.status
+    except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
+        return exc, "exception"
+
+
+def solve_batch_solutions(problems, max_pivots: int = 256, device=None, kernel: str = "auto"):
+    """Solve every ``(constraints, function)`` for its whole answer; returns
+    ``(solutions, statuses)``.
+
+    ``solutions[k]`` is the ``Solution`` of problem k -- ``x`` [m], ``duals`` [n], ``objective``,
+    ``basis`` [n], ``nonbasis`` [m] as numpy arrays and scalars, ``pivots`` -- equal to
+    ``SimplexMethod(...).solution()`` after ``solve(record_history=False)``, or the ``IndexError``
+    the reference would raise; ``statuses[k]`` as in ``solve_batch``.  The values stand whatever
+    the status.  Routing and launch splitting are ``solve_batch``'s; of a launch only the
+    solutions come back from the device (``solve_batch_arrays(solution=True, tables=False)``),
+    and no ``Info`` objects are built."""
+    problems = list(problems)
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
+    results = [None] * len(problems)
+    statuses = [None] * len(problems)
+    routes = _routes(problems, kernel)
+    for k, (c, f) in enumerate(problems):
+        if routes[k] == "single":
+            results[k], statuses[k] = _fallback_solution(c, f, max_pivots)
+    P = int(max_pivots)
+    for which, idx in _launches(problems, routes, max_pivots, False):
+        tabs, dims = pack([problems[k] for k in idx])
+        out = solve_batch_arrays(tabs, dims, max_pivots, False, device, kernel=which,
+                                 solution=True, tables=False)
+        for q, k in enumerate(idx):
+            n, m = int(dims[q, 0]), int(dims[q, 1])
+            status, np_ = int(out["status"][q]), int(out["npivots"][q])
+            results[k] = Solution(out["x"][q, :m].copy(), out["duals"][q, :n].copy(),
+                                  float(out["objective"][q]), out["basis"][q, :n].copy(),
+                                  out["nonbasis"][q, :m].copy(), np_)
+            if status == _lib.OPTIMUM:
+                statuses[k] = "optimum"
+            elif status in MESSAGES:
+                statuses[k] = "error"
+            elif status == _lib.PIVOT and np_ >= P:
+                statuses[k] = "cap"
+            else:
+                raise RuntimeError(f"unexpected batch status {status}")
     return results, statuses
 
 

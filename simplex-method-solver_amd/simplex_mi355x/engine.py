@@ -12,6 +12,7 @@ machine with an MI355X never takes it unless asked (``device="cpu"``).
 
 Additions (not in the reference, all opt-in): ``step()`` (one pick + pivot), ``solve()``
 (``get_solution`` with an optional pivot cap, or the chained no-history fast path),
+``solution()`` (every variable, the duals and the objective of the current table),
 ``pivots`` / ``pivot_log`` and ``status``.
 
 Deliberate differences, all on inputs the reference UI never produces (main.py:309-312 always
@@ -29,6 +30,7 @@ from __future__ import annotations
 
 import copy
 import gc
+from collections import namedtuple
 
 import numpy as np
 
@@ -38,6 +40,19 @@ from .device import DeviceTableau
 
 MESSAGES = {_lib.INCORRECT: "incorrect system",                  # simplex.py:89
             _lib.NOT_CONVERGE: "simplex method does not converge"}  # simplex.py:139
+
+
+# The whole answer of one LP (``SimplexMethod.solution()``, ``batch.solve_batch_solutions``).
+# Labels are int32 codes: k in 0..m-1 is 'x{k+1}', m + i is 'y{i+1}'.  ``x`` [m]: the "-b" entry of
+# the row labelled x{k+1}, else +0.0; ``duals`` [n]: the f-row entry of the column labelled
+# y{i+1} (in the tableau's sign), else +0.0; ``objective``: function[0]*x[0] + ... summed left to
+# right; ``basis`` [n] / ``nonbasis`` [m]: the labels of the rows / columns; ``pivots``: how many
+# pivots led here.
+Solution = namedtuple("Solution", "x duals objective basis nonbasis pivots")
+
+
+def _label_code(label: str, m: int) -> int:
+    return int(label[1:]) - 1 + (m if label[0] == 'y' else 0)
 
 
 class Error:
@@ -397,6 +412,32 @@ class SimplexMethod:
         x1 = vals[x1_i] if x1_i != self.invalid_index else 0
         x2 = vals[x2_i] if x2_i != self.invalid_index else 0
         return x1, x2
+
+    def solution(self) -> Solution:
+        """The current table's whole answer: ``find_optimum`` for every variable, the f-row
+        entries under the slack labels and the objective on the ORIGINAL function, with the
+        labels as int32 codes (``Solution``).  Values are read whatever ``status`` says; on the
+        caller's own table (before the first pivot) every x and dual is +0.0."""
+        n, m = self.n, self.m
+        basis = np.array([_label_code(s, m) for s in self.column[:n]], dtype=np.int32)
+        nonbasis = np.array([_label_code(s, m) for s in self.row[:m]], dtype=np.int32)
+        rows = [i for i in range(n) if basis[i] < m]
+        cols = [j for j in range(m) if nonbasis[j] >= m]
+        if self._pristine:        # the caller's own lists (labels may stand from an earlier run)
+            T = self._initial
+            vals = [T[i][m] for i in rows] + [T[n][j] if j < len(T[n]) else 0.0 for j in cols]
+        else:
+            vals = self._dev.values([(i, m) for i in rows] + [(n, j) for j in cols])
+        x = np.zeros(m, dtype=np.float64)
+        duals = np.zeros(n, dtype=np.float64)
+        if vals:
+            x[basis[rows]] = vals[:len(rows)]
+            duals[nonbasis[cols] - m] = vals[len(rows):]
+        xs = x.tolist()
+        objective = self.function[0] * xs[0]                 # each product rounded on its own,
+        for k in range(1, m):                                # summed strictly left to right
+            objective = objective + self.function[k] * xs[k]
+        return Solution(x, duals, float(objective), basis, nonbasis, self.pivots)
 
     # ---------------------------------------------------------------- the hot path -------
     def pick_element(self) -> (bool, int, int, float):
