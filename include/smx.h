@@ -356,6 +356,10 @@ int64_t smx_tune_resident_timeout(int64_t ticks);
  * uses a different epoch for each of 4095 consecutive launches on it, and zeroes it again
  * before an epoch value comes round again; k < 2^20 - 1.  A hand-off that does not complete
  * within 2 s sets ctl->dec[0][0] = 1 and the kernel returns (the table is then undefined).
+ * Rings shorter than the launch (log_cap < k; log_cap < pivots per block in the block chain's
+ * persistent planner): a slot is then written more than once inside one launch, by different
+ * workgroups, and holds the LAST pivot that maps to it -- those x-history stores are written
+ * through and ordered by the hand-offs.
  * smx_tune_resident: -1 never, 0 automatic, > 0 that many workgroups (<= 256), -2 keeps;
  * returns the previous setting.
  * smx_resident_trace (diagnostic): device buffer of 64 x G x 8 uint64 s_memrealtime stamps for

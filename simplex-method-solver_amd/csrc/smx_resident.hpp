@@ -636,12 +636,28 @@ __global__ __launch_bounds__(kResBlock) void k_resident(
         }
         __syncthreads();
         stamp(s, 5);
-        if (tid < 2 && xhist != nullptr && log_cap > 0) {   // (x1, x2) after pivot kk
-            const int code = tid ? xp1 : xp0;
-            if (code >= row0 && code < row0 + nl)
-                xhist[2 * (kk % log_cap) + tid] = s_T[(code - row0) * ldl + m];
-            else if (code < 0 && g == 0)
-                xhist[2 * (kk % log_cap) + tid] = 0.0;
+        if (xhist != nullptr && log_cap > 0) {   // (x1, x2) after pivot kk
+            // A ring shorter than the chain has a slot written again log_cap pivots later inside
+            // this launch, possibly by another workgroup (the new owner of the label's row, or
+            // workgroup 0 for a label that left the basis) behind another L2: plain stores of the
+            // two would reach memory in either order.  Such a ring is written through (sc1) and
+            // drained before this wave's next record, so every store of a pivot is in memory
+            // before any workgroup decides the next one.  Longer rings keep the plain stores.
+            const bool wt = log_cap < k;
+            if (tid < 2) {
+                const int code = tid ? xp1 : xp0;
+                double* dst = xhist + 2 * (kk % log_cap) + tid;
+                double v = 0.0;
+                const bool own = code >= row0 && code < row0 + nl;
+                if (own) v = s_T[(code - row0) * ldl + m];
+                if (own || (code < 0 && g == 0)) {
+                    if (wt)
+                        st_sc1(reinterpret_cast<uint64_t*>(dst), dbits(v));
+                    else
+                        *dst = v;
+                }
+            }
+            if (wt && wid == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
     }
 

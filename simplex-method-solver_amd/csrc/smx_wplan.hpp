@@ -226,6 +226,18 @@ __global__ __launch_bounds__(kWinNT) void k_blk_wplan(
     const int ms = __builtin_amdgcn_readfirstlane(win_slot(m, nwin, C));
     double* __restrict__ mT = blk_mulT(mul, rows + 1);
     const bool want_x = xhist && log_cap > 0;
+    // A ring shorter than the block has a slot written twice inside this launch, possibly by two
+    // workgroups (the owner of a label's row; workgroup 0 for a label outside the basis) behind
+    // different L2s, whose plain stores reach memory in either order: such a ring is written
+    // through (sc1) and drained before the workgroup's next record, so every store of a step is in
+    // memory before any workgroup decides the next one.  Longer rings keep the plain stores.
+    const bool x_wt = want_x && log_cap < P;
+    auto xput = [&](double* p, double v) {
+        if (WP_COLD(x_wt))
+            st_sc1(reinterpret_cast<uint64_t*>(p), dbits(v));
+        else
+            *p = v;
+    };
     auto bail = [&](int D) {
         // a hand-off that never came (a workgroup not resident or stalled): stop the chain; the
         // host reports it (device.py sync_state, RESIDENT_TIMEOUT)
@@ -530,8 +542,8 @@ __global__ __launch_bounds__(kWinNT) void k_blk_wplan(
             ctl->xpos[sp ^ 1][0] = hx0;
             ctl->xpos[sp ^ 1][1] = hx1;
             if (want_x) {                          // non-basic labels: 0 (simplex.py:60-66)
-                if (hx0 < 0) xhist[2 * (kpiv % log_cap)] = 0.0;
-                if (hx1 < 0) xhist[2 * (kpiv % log_cap) + 1] = 0.0;
+                if (hx0 < 0) xput(xhist + 2 * (kpiv % log_cap), 0.0);
+                if (hx1 < 0) xput(xhist + 2 * (kpiv % log_cap) + 1, 0.0);
             }
             if (L == P) h->cfs[blk_slot(L, P, bn)] = cfn;
         }
@@ -625,8 +637,8 @@ __global__ __launch_bounds__(kWinNT) void k_blk_wplan(
                         mT[(int64_t)D * (rows + 1) + i] = myc;
                         s_mrow[wid][ub + lane][D] = myc;
                         if (want_x) {
-                            if (i == hx0) xhist[hslot] = mybv;
-                            if (i == hx1) xhist[hslot + 1] = mybv;
+                            if (i == hx0) xput(xhist + hslot, mybv);
+                            if (i == hx1) xput(xhist + hslot + 1, mybv);
                         }
                         blk_rec_add(R, i, mybv, cfn != SMX_NONE, mya);
                     }
@@ -637,6 +649,9 @@ __global__ __launch_bounds__(kWinNT) void k_blk_wplan(
             rowpass(std::integral_constant<int, kWinBatch / 2>{});
         else
             rowpass(std::integral_constant<int, kWinBatch>{});
+        if (WP_COLD(x_wt) && ((b == 0 && wid == 0) || (hx0 >= i0 && hx0 < i1) ||
+                              (hx1 >= i0 && hx1 < i1)))
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's x-history stores
         SMX_BLK_STAMP(5);
         SMX_BLK_STAMP_WMAX(6);
         // ---- the records of step L: granules (L < P) or memory (the next block's first) -------

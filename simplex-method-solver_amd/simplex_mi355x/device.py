@@ -199,7 +199,10 @@ class DeviceTableau:
     def _ring(self, buf, start, stop, dtype):
         if stop <= start:
             return np.zeros((0, 2), dtype=dtype)
-        if stop - start > self.log_cap:
+        self.settle()
+        # wider than the ring, or begun before the oldest pivot the ring still holds: those slots
+        # carry newer pivots by now
+        if stop - start > self.log_cap or start < self.step - self.log_cap:
             raise RuntimeError("pivot log overrun: drain the log more often")
         pos = np.arange(start, stop) % self.log_cap
         lo, hi = int(pos.min()), int(pos.max()) + 1
