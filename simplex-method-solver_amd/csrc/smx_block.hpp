@@ -1340,6 +1340,42 @@ __device__ unsigned long long g_path_cnt[kPcCount];
 // rows spread over ~K times as many workgroups.  The pivot-row slices are restaged per item.
 __device__ int g_sweep_items = 16;
 
+// FORM 7: the LDS layout in row pairs.  FORM 5's grid, chunk ownership, staging and chunk flags; a
+// lane keeps TWO rows of its two columns (rows i0 and i0 + qs of its wave), so each ds_read_b128
+// of a pivot's row slice and of its (e, y) feeds four independent chains instead of two: half the
+// LDS instructions and returned bytes per element-pivot, and the per-row costs (the scalar round
+// trip for flags and multipliers, the input vote, the address arithmetic, the vmcnt hand-over)
+// once per two rows.  Two rows' multipliers of all 24 pivots would be 96 scalar registers (round 2
+// dropped two-row batches for that: the scalars spilled into vector lanes), so the
+// pivots are taken in phases of kPairPhase: 2 rows x 12 multipliers are the 48 scalar registers
+// one row x 24 takes in FORM 5, and each phase's multipliers are loaded where the phase begins.
+// A pair is fast only when both rows are (flags 1, one vote over both rows' inputs); any other
+// pair, and an odd row left at the end, goes row by row through FORM 5's single-row code,
+// unchanged.
+constexpr int kPairPhase = 12;
+
+// One pivot of a row pair's fast path: four chains, each the one-row fast path's six
+// instructions in its order (two products, their difference, t = n y, r = fma(-e, t, n),
+// fma(r, y, t)).
+__device__ __forceinline__ void blk_pair_step(dbl2& va, dbl2& vb, dbl2 p, dbl2 ey, double ma,
+                                              double mb) {
+    const double e = ey[0], y = ey[1];
+    double n[4];
+    n[0] = va[0] * e - p[0] * ma;
+    n[1] = va[1] * e - p[1] * ma;
+    n[2] = vb[0] * e - p[0] * mb;
+    n[3] = vb[1] * e - p[1] * mb;
+    double rr[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double tq = n[k] * y;
+        const double r = fma(-e, tq, n[k]);
+        rr[k] = fma(r, y, tq);
+    }
+    va = dbl2{rr[0], rr[1]};
+    vb = dbl2{rr[2], rr[3]};
+}
+
 template <int P, int FORM>
 __device__ __forceinline__ void blk_sweep_body_flag(const double* Tin, double* Tout, int64_t ld,
                                                     int R, int C, const BlkHdr* __restrict__ h,
@@ -1347,6 +1383,7 @@ __device__ __forceinline__ void blk_sweep_body_flag(const double* Tin, double* T
                                                     const double* __restrict__ mul) {
     constexpr bool LDS = FORM >= 5;
     constexpr bool ITEMS = FORM == 6;
+    constexpr bool PAIRS = FORM == 7;
     __shared__ dbl2 s_pr[LDS ? P : 1][kWave];
     __shared__ dbl2 s_ey[LDS ? P : 1];
     // the zero-extended path's scalars (fd_zneg): the chain carries g_q = -sgn(e_q) x_{q+1}, so
@@ -1627,6 +1664,71 @@ __device__ __forceinline__ void blk_sweep_body_flag(const double* Tin, double* T
         if (j < C)
             __builtin_nontemporal_store(v0, reinterpret_cast<dbl2*>(Tout + (int64_t)i0 * ld + j));
     };
+    // FORM 7: rows ia and ia + qs together (xa, xb: their inputs; hi: the end of the wave's rows)
+    auto pairf = [&](dbl2 xa, dbl2 xb, int ia, int hi) {
+        constexpr int NPH = (P + kPairPhase - 1) / kPairPhase;
+        constexpr int P0 = P < kPairPhase ? P : kPairPhase;
+        const int ib = ia + qs;
+        const bool two = ib < hi;   // (false: an odd row left at the end of the wave's rows)
+        const int ibc = two ? ib : ia;   // (nothing read past the table's rows)
+        const double* ma = mul + (int64_t)ia * kBlkMax;
+        const double* mb = mul + (int64_t)ibc * kBlkMax;
+        int rfa = rfl[ia], rfb = rfl[ibc];
+        asm volatile("" : "+s"(rfa));
+        asm volatile("" : "+s"(rfb));
+        const uint32_t xt = max(max((uint32_t)__double2hiint(xa[0]) << 1,
+                                    (uint32_t)__double2hiint(xa[1]) << 1),
+                                max((uint32_t)__double2hiint(xb[0]) << 1,
+                                    (uint32_t)__double2hiint(xb[1]) << 1));
+        if (two && chunk_free && rfa == 1 && rfb == 1 && __all(xt < kBndXMax)) {
+            SMX_PC(kPcFast);   // two (row, chunk) units
+            SMX_PC(kPcFast);
+            dbl2 va = xa, vb = xb;
+            double pa[P0], pb[P0];
+#pragma unroll
+            for (int ph = 0; ph < NPH; ++ph) {
+                const int q0 = ph * kPairPhase;
+                const int nq = P - q0 < kPairPhase ? P - q0 : kPairPhase;
+                // This phase's multipliers of both rows, one scalar round trip, waited for in
+                // place.  Their offset passes through an asm together with the chains' values, so
+                // the loads are issued here, after the phase before, and not hoisted above it
+                // (where two phases' scalars would be live and spill); the first phase's too:
+                // loaded beside the flags, ahead of this branch, all 48 were spilled to vector
+                // lanes on the way in and read back one by one here.  (The offset, not the
+                // pointers: a pointer handed to an asm counts as captured, and every load of the
+                // multipliers then turns into a vector load.)
+                int o = q0;
+                asm volatile("" : "+s"(o) : "v"(va), "v"(vb));
+#pragma unroll
+                for (int q = 0; q < nq; ++q) {
+                    pa[q] = ma[o + q];
+                    pb[q] = mb[o + q];
+                }
+#pragma unroll
+                for (int q = 0; q < nq; ++q) {
+                    asm volatile("" : "+s"(pa[q]));
+                    asm volatile("" : "+s"(pb[q]));
+                }
+#pragma unroll
+                for (int q = 0; q < nq; ++q)
+                    blk_pair_step(va, vb, s_pr[q0 + q][lane], s_ey[q0 + q], pa[q], pb[q]);
+            }
+            // (the values pinned here: left alone, the compiler sinks the last phase's arithmetic
+            // into the store's `j < C` branch and hoists every LDS read of it above the branch --
+            // 124 VGPRs instead of 60 at P = 24)
+            asm volatile("" : "+v"(va), "+v"(vb));
+            if (j < C) {
+                __builtin_nontemporal_store(va,
+                                            reinterpret_cast<dbl2*>(Tout + (int64_t)ia * ld + j));
+                __builtin_nontemporal_store(vb,
+                                            reinterpret_cast<dbl2*>(Tout + (int64_t)ib * ld + j));
+            }
+        } else {
+            // row by row (each loads its own flag and multipliers: not the bench's path)
+#pragma nounroll
+            for (int s = 0; s < (two ? 2 : 1); ++s) rowf(s ? xb : xa, s ? ib : ia);
+        }
+    };
     if constexpr (!ITEMS) {
         if (base >= R) return;
     }
@@ -1651,6 +1753,31 @@ __device__ __forceinline__ void blk_sweep_body_flag(const double* Tin, double* T
         // its load are the previous row's store and the other set's load (vmcnt(2); vmcnt(1)
         // first)
         const int r0 = lo + base;
+        if constexpr (PAIRS) {
+            // prefetch depth 1 over pairs: before a pair's registers are used, the ops issued
+            // after its two loads are the previous pair's two stores (one only for an odd last
+            // row, and then no pair follows) and the other pair's two loads: vmcnt(4)
+            int i0 = r0;
+            dbl2 a0 = ldc(i0), a1 = ldc(i0 + qs);
+            dbl2 b0 = ldc(i0 + 2 * qs), b1 = ldc(i0 + 3 * qs);
+            asm volatile("s_waitcnt vmcnt(2)" : "+v"(a0), "+v"(a1) :: "memory");
+            for (;;) {
+                pairf(a0, a1, i0, hi);
+                i0 += 2 * qs;
+                if (i0 >= hi) break;
+                a0 = ldc(i0 + 2 * qs);
+                a1 = ldc(i0 + 3 * qs);
+                asm volatile("s_waitcnt vmcnt(4)" : "+v"(b0), "+v"(b1) :: "memory");
+                pairf(b0, b1, i0, hi);
+                i0 += 2 * qs;
+                if (i0 >= hi) break;
+                b0 = ldc(i0 + 2 * qs);
+                b1 = ldc(i0 + 3 * qs);
+                asm volatile("s_waitcnt vmcnt(4)" : "+v"(a0), "+v"(a1) :: "memory");
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            continue;
+        }
         dbl2 a = ldc(r0), b = ldc(r0 + qs);
         asm volatile("s_waitcnt vmcnt(1)" : "+v"(a) :: "memory");
         for (int i0 = r0; i0 < hi; i0 += 2 * qs) {
@@ -1733,7 +1860,7 @@ __device__ __forceinline__ double* blk_out(double* b_in, double* b_other, int ip
 
 // The sweep of a block that applied all P of its pivots (h->peff == P; otherwise it does nothing
 // and k_blk_sweep_rest handles the block): one body per kernel, so the register allocation is
-// that body's alone.  FORM 4 / 5: blk_sweep_body_flag's layouts.  Output per blk_out.
+// that body's alone.  FORM 4 / 5 / 6 / 7: blk_sweep_body_flag's layouts.  Output per blk_out.
 template <int P, int FORM>
 __global__ __launch_bounds__(kUpdBlock) void k_blk_sweep(double* b_in, double* b_other, int64_t ld,
                                                          int R, int C,

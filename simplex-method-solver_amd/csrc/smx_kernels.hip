@@ -518,7 +518,7 @@ using BshPackFn = void (*)(const double*, int64_t, int, int, int, int, int, cons
                            const BlkHdr*, const smx_part*, int, const double*, const double*,
                            double*);
 
-// Sweep kernels by pivot count (1..kBlkMax) and layout (FORM 4 / 5, blk_sweep_body_flag)
+// Sweep kernels by pivot count (1..kBlkMax) and layout (FORM 4 / 5 / 6 / 7, blk_sweep_body_flag)
 template <int FORM, int... Is>
 BlkSweepFn blk_sweep_pick(int P, std::integer_sequence<int, Is...>) {
     static const BlkSweepFn t[] = {k_blk_sweep<Is + 1, FORM>...};
@@ -526,7 +526,8 @@ BlkSweepFn blk_sweep_pick(int P, std::integer_sequence<int, Is...>) {
 }
 BlkSweepFn blk_sweep_fn(int P, int form) {
     using All = std::make_integer_sequence<int, kBlkMax>;
-    return form == 6 ? blk_sweep_pick<6>(P, All{})
+    return form == 7 ? blk_sweep_pick<7>(P, All{})
+           : form == 6 ? blk_sweep_pick<6>(P, All{})
                      : form == 5 ? blk_sweep_pick<5>(P, All{}) : blk_sweep_pick<4>(P, All{});
 }
 
@@ -688,10 +689,19 @@ int launch_blk_publish(bool sh, const smx_shape& s, int parity, int bn, smx_ctl*
 
 // Sweep layout (smx_tune_block_form): 0 automatic -- the register layout (4) up to kSweepRegMaxP
 // pivots, the LDS layout (5) beyond and wherever the register layout's grid cannot give every
-// wave one chunk; 4 / 5 forced (tests, A/B timing).
+// wave one chunk; 4 / 5 / 6 / 7 forced (tests, A/B timing).
 int g_block_form = 0;
 constexpr int kSweepRegMaxP = 12;
 constexpr int64_t kSweepItemRows = 2048;   // rows per wave from which FORM 6 is automatic
+// FORM 7 (row pairs) is automatic from 20 pivots per sweep and 64 rows per wave, where it was
+// measured against FORM 5 (parent and new build interleaved on one box, mean sweep in us, 6 runs
+// each, profiles/r07/): 16384^2 (256 rows per wave) 1700 -> 1580 / 1833 -> 1731 / 1887 -> 1787 /
+// 1974 -> 1865 at 20 / 22 / 23 / 24 pivots, every new run below every parent run; 8192^2 (64 rows
+// per wave) 363 -> 351 at 20 and 428 -> 419 at 24 (ranges 425-434 and 410-426: they touch).  At
+// 4096^2 (16 rows per wave) 131 -> 128 at 24 and 94 -> 93 at 16: inside the spread, FORM 5 stays;
+// 13-19 pivots were not measured.
+constexpr int kSweepPairMinP = 20;
+constexpr int64_t kSweepPairRows = 64;
 
 // Grid of the LDS layout: a multiple of the chunks per row (every workgroup keeps one chunk),
 // as many workgroups as are resident at bpc per CU, at least one per chunk.
@@ -713,7 +723,7 @@ int launch_block_sweep(bool sh, double* tin, double* tother, const smx_shape& s,
                        int in_idx = 0, int ipx_part = 0, smx_ctl* pub_ctl = nullptr,
                        int pub_bn = 0, int pub_parity = 0) {
     const int nchunks = (s.m + 1 + 2 * kWave - 1) / (2 * kWave);
-    int form = g_block_form >= 4 && g_block_form <= 6 ? g_block_form
+    int form = g_block_form >= 4 && g_block_form <= 7 ? g_block_form
                                                       : (P > kSweepRegMaxP ? 5 : 4);
     int grid = 0;
     if (form == 4) {
@@ -730,13 +740,18 @@ int launch_block_sweep(bool sh, double* tin, double* tother, const smx_shape& s,
         // wave) it cost 7 %, at 8192^2 35 % (profiles/r06ag/)
         const int64_t per = sweep_grid_lds(s, g_blocks_per_cu > 0 ? g_blocks_per_cu : 8) / nchunks;
         if ((int64_t)(s.rows + 1) >= per * kUpdWaves * kSweepItemRows) form = 6;
+        else if (P >= kSweepPairMinP && (int64_t)(s.rows + 1) >= per * kUpdWaves * kSweepPairRows)
+            form = 7;
     }
     BlkSweepFn fn = blk_sweep_fn(P, form);
     if (form >= 5)   // a grid of 8 workgroups per CU.  At P = 20 only 7 are resident (P KiB of
                      // pivot-row slices in LDS, ~106 SGPRs), but the sweep is fp64-issue-bound
                      // there and the grid sized for 8 is as fast as 7 and faster than the
                      // occupancy API's 6: 16384^2, 200 pivots, mean sweep 1.464 / 1.488 / 1.503 ms
-                     // at 8 / 7 / 6 (profiles/r05a/).  smx_tune_set(-2, bpc) overrides it.
+                     // at 8 / 7 / 6 (profiles/r05a/).  FORM 7 (60 VGPRs at P = 24, 6 resident):
+                     // mean sweep 1865 / 1876 / 1906 us at 24 pivots and 1580 / 1584 / 1608 at 20
+                     // with the grid sized for 8 / 7 / 6 (profiles/r07/ab2_sweeps.jsonl): 8 stays.
+                     // smx_tune_set(-2, bpc) overrides it.
         grid = sweep_grid_lds(s, g_blocks_per_cu > 0 ? g_blocks_per_cu : 8);
     BlkHdr* hs = reinterpret_cast<BlkHdr*>(blk);
     const BlkHdr* h = reinterpret_cast<const BlkHdr*>(blk + kBlkHdrBytes * slot);
@@ -1711,7 +1726,7 @@ int smx_diag_path_counts(int64_t* out, int32_t count, int32_t clear) {
 
 int smx_tune_block_form(int32_t form) {
     const int prev = g_block_form;
-    if (form == 0 || (form >= 4 && form <= 6)) g_block_form = form;
+    if (form == 0 || (form >= 4 && form <= 7)) g_block_form = form;
     return prev;
 }
 

@@ -323,7 +323,8 @@ def tune_block_planner(planner: int = -1, nwin: int = -1) -> int:
 
 def tune_block_form(form: int = -1) -> int:
     """smx_tune_block_form: 0 automatic, 4 pivot-row slices in registers, 5 in LDS, 6 in LDS by
-    work items (rows in segments, each at another column chunk); any other
+    work items (rows in segments, each at another column chunk), 7 in LDS by row pairs (two rows
+    per lane share each pivot's LDS operands; multipliers in phases of 12 pivots); any other
     value only queries; returns the previous setting."""
     return int(load().smx_tune_block_form(form))
 
