@@ -397,7 +397,7 @@ int smx_fastdiv_check_bounded(const double* num, const double* den, int64_t coun
  * rows flagged 0 / 3, inputs out of bounds on a free chunk and flag-1 row, units in chunks whose
  * pivots / pivot-row values fail the bounds, then per wave the shader clock (s_memtime) and the
  * 100 MHz real time (s_memrealtime) over its sweep body -- their ratio is the clock the sweep
- * ran at (smx_block.hpp kPc*).
+ * ran at (smx_sweep.hpp kPc*).
  * Synchronises the device.  Returns the number of counters, or -hipErrorNotSupported in the
  * product build (the counters exist only in libsmx_diag.so, `make -C csrc diag`). */
 int smx_diag_path_counts(int64_t* out, int32_t count, int32_t clear);
@@ -430,7 +430,7 @@ int smx_tune_block(int32_t pivots);
  * (k_blk_step).  nwin: window slots 2..64 (0 = 64, the default; -1 keeps it).  Same decisions
  * and bits either way.  Returns the previous planner. */
 int smx_tune_block_planner(int32_t planner, int32_t nwin);
-/* Layout of the block sweep (k_blk_sweep, csrc/smx_block.hpp): 0 automatic (the default: pivot-
+/* Layout of the block sweep (k_blk_sweep, csrc/smx_sweep.hpp): 0 automatic (the default: pivot-
  * row slices in registers up to 12 pivots per sweep, in LDS shared by a workgroup's waves beyond,
  * and wherever the register layout's grid cannot give every wave one column chunk), 4 registers,
  * 5 LDS, 6 LDS in work items (every workgroup's rows in K segments, each at another column chunk:

@@ -15,6 +15,7 @@
 //                     objective and labels, one wavefront per LP)
 //   smx_resident.hpp  k_resident: the whole pivot loop in one persistent launch, tableau in LDS
 //   smx_block.hpp     k_blk_*: P pivots per HBM sweep, decisions planned from the sweep's input
+//   smx_sweep.hpp     k_blk_sweep, k_blk_sweep_rest: the sweep itself
 // and this file holds the host side: grid sizing, variants, chains, graphs, RCCL, the C ABI.
 //
 // Arithmetic parity: every element is (t*e - pr*pc)/e with each op rounded on its own, exactly
@@ -61,6 +62,7 @@ static_assert(sizeof(smx_part) == 32, "smx_part layout");
 #include "smx_solution.hpp"
 #include "smx_resident.hpp"
 #include "smx_block.hpp"
+#include "smx_sweep.hpp"
 #include "smx_window.hpp"
 #include "smx_wplan.hpp"
 #include "smx_host.hpp"

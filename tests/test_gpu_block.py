@@ -1,5 +1,6 @@
-"""GPU parity of block pivots (smx_block_run, csrc/smx_block.hpp): P pivots planned from the
-block's input table and applied in one HBM sweep; every test runs with both planners: the window
+"""GPU parity of block pivots (smx_block_run; the planner is csrc/smx_block.hpp, the sweep
+csrc/smx_sweep.hpp): P pivots planned from the block's input table and applied in one HBM sweep;
+every test runs with both planners: the window
 planner (the default: the first columns of every row kept current step by step, k_blk_wstep) and
 the register-form chains (k_blk_step<L>).  Bit-exact against the golden fixtures, the C
 oracle and the one-pivot-per-sweep chain, for block sizes 1..24, both sweep layouts (pivot-row
@@ -192,7 +193,7 @@ def test_block_vs_oracle(block_mode, sweep_form, kind, n, m, k, chunk, P, form):
 @pytest.mark.parametrize("P", [10, 12, 16, 20, 24])
 @pytest.mark.parametrize("form", [4, 5, 6])
 def test_block_bounded_fast_path_edges_vs_oracle(block_mode, sweep_form, P, form):
-    """The one-row sweep's unchecked fast path (smx_block.hpp, kBndSpan) next to its fallbacks in
+    """The one-row sweep's unchecked fast path (smx_sweep.hpp; the bounds: smx_block.hpp, kBndSpan) next to its fallbacks in
     one table: rows scaled past 2^101 (input bound), rows scaled to ~2^-60 (small numerators),
     columns scaled to ~2^-99 (pivot-row values below 2^-100: the chunk falls back), exact zeros
     (zero multipliers and pivot-row values), signed zeros -- bit-exact against the C oracle."""

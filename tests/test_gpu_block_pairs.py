@@ -1,5 +1,5 @@
 """GPU parity of the row-pair sweep layout (smx_tune_block_form(7), blk_sweep_body_flag<P, 7> in
-csrc/smx_block.hpp): a lane keeps two rows of its two columns, so each LDS read of a pivot's row
+csrc/smx_sweep.hpp): a lane keeps two rows of its two columns, so each LDS read of a pivot's row
 slice and of (e, y) feeds four chains, and the rows' multipliers arrive in phases of 12 pivots.
 
 Bit-exact against the C oracle with pairs, odd tails and mixed pairs (rows of one pair on
@@ -121,6 +121,40 @@ def test_mixed_pairs_vs_oracle(block_mode, sweep_form, small_grid):
     block_mode(13)
     n, m = 1000, 1023
     _run_vs_oracle(mixed_pair_table(n, m), n, m, 13)
+
+
+@pytest.mark.parametrize("m", [1023, 1100])
+def test_forms_agree_on_mixed_paths(block_mode, sweep_form, small_grid, m):
+    """mixed_pair_table under every sweep layout (forms 4, 5, 6, 7), 13 pivots per sweep, 2 x 13 + 3
+    pivots cut as _chunks(13): the four pivot logs and the four tables' bits are equal, and form
+    5's equal the C oracle's.  A wave owns 7-9 rows, so both register sets of each prefetch loop
+    rotate, with an odd tail, a ragged last chunk (m = 1100) and a second pair phase of one pivot;
+    the rows fall on every sweep path.  (Form 4 runs as form 5 where its wave count does not
+    divide: nothing here depends on which kernel ran.)"""
+    from oracle import c_oracle
+    import simplex
+    n, P = 1000, 13
+    T = mixed_pair_table(n, m)
+    block_mode(P)
+    k = sum(_chunks(P))
+    out = {}
+    for form in (4, 5, 6, 7):
+        sweep_form(form)
+        sm = simplex.SimplexMethod(T[:n].tolist(), T[n, :m].tolist())
+        assert sm._dev.block_plan()[1] == P
+        for c in _chunks(P):
+            sm.solve(record_history=False, max_pivots=c, chunk=c)
+        out[form] = (sm.pivots, list(sm.pivot_log), sm._dev.download().view(np.int64).copy())
+    Tref, st, done, log = c_oracle.run(T, n, m, m, k, threads=8)
+    assert done == k, "the LP must run all k pivots (no terminal outcome)"
+    assert out[5][0] == done
+    assert out[5][1] == [tuple(map(int, x)) for x in log]
+    assert np.array_equal(out[5][2][:n], Tref[:n].view(np.int64))
+    assert np.array_equal(out[5][2][n, :m], Tref[n, :m].view(np.int64))
+    for form in (4, 6, 7):
+        assert out[form][0] == out[5][0], form
+        assert out[form][1] == out[5][1], form
+        assert np.array_equal(out[form][2], out[5][2]), form
 
 
 def test_form7_equals_form5(block_mode, sweep_form):

@@ -5,7 +5,7 @@
 
 One JSON line per block of `pivots` pivots: the sweep's HIP-event time, and -- with the
 diagnostic build (`make -C simplex-method-solver_amd/csrc diag`, loaded through SMX_LIB) -- the
-number of (row, 128-column chunk) units per path of blk_sweep_body_flag (smx_block.hpp kPc*:
+number of (row, 128-column chunk) units per path of blk_sweep_body_flag (smx_sweep.hpp kPc*:
 fast / zero-extended / window-tracked / window failed -> exact / exact directly, plus why units
 missed the fast path).  `--idle S` sleeps S seconds before every block (a sweep that is fast after
 a pause but slow back to back is the clock, not the data).  A last line sums the run.
