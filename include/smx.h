@@ -247,6 +247,48 @@ int smx_batch_solution(const double* final, const int32_t* dims, int32_t B, int3
  * every shape a batch kernel takes is inside).  The single statement of that envelope. */
 int64_t smx_batch_solution_lds_bytes(int32_t Rmax, int32_t ldb);
 
+/* ---- sensitivity ranging: rhs and cost ranges of a final table (smx_ranging.hpp) -------------
+ * For which change d of a constraint's constant t_i, or of a cost function[k], the final basis
+ * stays the one the method stopped at.  T is the final table ([n+1][m+1], f-row = row n, "-b" =
+ * column m), basis[p] the label of row p and nonbasis[j] of column j, as smx_batch_solution writes
+ * them (k < m is 'x{k+1}', m + i is 'y{i+1}').  The table reads
+ *   label(row p) = sum_j T[p][j] * label(col j) + T[p][m],
+ * the method stops where T[p][m] >= 0 (p < n) and T[n][j] >= 0 (j < m), and adding d to t_i or to
+ * function[k] moves one of those two families linearly in d: the range is the d-interval over
+ * which it stays >= 0.  The position of a label decides the rule:
+ *   row p,    basis[p] = m + i     rhs_lo[i] = T[p][m] with its sign bit flipped; rhs_hi[i] = +inf
+ *   column j, nonbasis[j] = m + i  for every row p < n: a = T[p][j], q = T[p][m] / a (one IEEE
+ *                                  division); a > 0: q is a candidate for rhs_hi[i] (a minimum),
+ *                                  a < 0: for rhs_lo[i] (a maximum)
+ *   column j, nonbasis[j] = k < m  cost_lo[k] = T[n][j] with its sign bit flipped; cost_hi[k] = +inf
+ *   row p,    basis[p] = k < m     for every column j < m: a = T[p][j], q = (-T[n][j]) / a;
+ *                                  a > 0: q is a candidate for cost_lo[k] (a maximum), a < 0: for
+ *                                  cost_hi[k] (a minimum)
+ * A zero or NaN a is skipped.  A bound without a candidate is +inf (minimum) or -inf (maximum); a
+ * bound with a NaN candidate is the quiet NaN 0x7ff8000000000000; otherwise it is the minimum /
+ * maximum under the total order in which -0.0 stands below +0.0.  So no bound depends on the order
+ * of reduction.  No FMA; `/` is the correctly rounded division.  A label code outside 0..n+m-1 is
+ * skipped and an output element no valid code names holds +0.0, as does the padding past n / m.
+ * Values are formed whatever the status; at an optimum lo <= 0 <= hi.
+ *
+ * smx_batch_ranging (device pointers, after smx_batch_solution): final fp64 [B][Rmax][ldb], dims
+ * int32 [B][3], basis int32 [B][Rmax], nonbasis int32 [B][ldb]; outputs rhs_lo, rhs_hi fp64
+ * [B][Rmax] and cost_lo, cost_hi fp64 [B][ldb].  A problem without 1 <= n_b < Rmax and
+ * 1 <= m_b < ldb gets the padding only.  Returns hipErrorInvalidValue (1) before any HIP call for
+ * B < 0, a shape outside smx_batch_ranging_fits or, with B > 0, a null pointer; B == 0 returns 0
+ * without a launch. */
+int smx_batch_ranging(const double* final, const int32_t* dims, int32_t B, int32_t Rmax,
+                      int32_t ldb, const int32_t* basis, const int32_t* nonbasis, double* rhs_lo,
+                      double* rhs_hi, double* cost_lo, double* cost_hi, void* stream);
+/* Host only: 1 inside the envelope (Rmax >= 2, ldb >= 2, Rmax + ldb <= 8192: that of
+ * smx_batch_solution, whose labels are the input), else 0. */
+int smx_batch_ranging_fits(int32_t Rmax, int32_t ldb);
+/* The same rules on one HOST table with leading dimension ld >= m + 1 (synchronous); outputs
+ * rhs_lo, rhs_hi [n] and cost_lo, cost_hi [m].  -1 for a null pointer, n < 1, m < 1 or ld < m + 1. */
+int smx_host_ranging(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                     const int32_t* nonbasis, double* rhs_lo, double* rhs_hi, double* cost_lo,
+                     double* cost_hi);
+
 /* ---- row-sharded engine (one process per GPU; exchange = caller's all-gather) ----------
  * Local tableau: shape->rows constraint rows (global rows row0 .. row0+rows-1) + a replica
  * of the f-row as local row `rows`.  Per pivot:

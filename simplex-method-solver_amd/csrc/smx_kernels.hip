@@ -13,6 +13,8 @@
 //   smx_batch_gm.hpp  k_batch_gm (one LP past the LDS edge per workgroup, tableau in global memory)
 //   smx_solution.hpp  k_batch_solution (a batch's final tables and pivot logs -> x, duals,
 //                     objective and labels, one wavefront per LP)
+//   smx_ranging.hpp   k_batch_ranging (a batch's final tables and labels -> rhs and cost ranges,
+//                     one workgroup per LP) and host_ranging, its host twin
 //   smx_resident.hpp  k_resident: the whole pivot loop in one persistent launch, tableau in LDS
 //   smx_block.hpp     k_blk_*: P pivots per HBM sweep, decisions planned from the sweep's input
 //   smx_sweep.hpp     k_blk_sweep, k_blk_sweep_rest: the sweep itself
@@ -60,6 +62,7 @@ static_assert(sizeof(smx_part) == 32, "smx_part layout");
 #include "smx_batch_wg.hpp"
 #include "smx_batch_gm.hpp"
 #include "smx_solution.hpp"
+#include "smx_ranging.hpp"
 #include "smx_resident.hpp"
 #include "smx_block.hpp"
 #include "smx_sweep.hpp"
@@ -1292,6 +1295,32 @@ int smx_batch_solution(const double* final, const int32_t* dims, int32_t B, int3
                        dim3(kSolWaves * kWave), (size_t)lds, S(stream), final, dims, B, Rmax, ldb,
                        max_pivots, rc, npivots, func, x, duals, objective, basis, nonbasis);
     return (int)hipGetLastError();
+}
+
+// ---- a batch's rhs and cost ranges from its final tables and labels (smx_ranging.hpp) ---------
+// The envelope is smx_batch_solution's (its labels are the input): static LDS of a fixed size.
+int smx_batch_ranging_fits(int32_t Rmax, int32_t ldb) { return sol_lds_bytes(Rmax, ldb) >= 0; }
+
+int smx_batch_ranging(const double* final, const int32_t* dims, int32_t B, int32_t Rmax,
+                      int32_t ldb, const int32_t* basis, const int32_t* nonbasis, double* rhs_lo,
+                      double* rhs_hi, double* cost_lo, double* cost_hi, void* stream) {
+    if (B < 0 || sol_lds_bytes(Rmax, ldb) < 0) return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    if (!final || !dims || !basis || !nonbasis || !rhs_lo || !rhs_hi || !cost_lo || !cost_hi)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_batch_ranging, dim3(B), dim3(kRngBlock), 0, S(stream), final, dims, B,
+                       Rmax, ldb, basis, nonbasis, rhs_lo, rhs_hi, cost_lo, cost_hi);
+    return (int)hipGetLastError();
+}
+
+int smx_host_ranging(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                     const int32_t* nonbasis, double* rhs_lo, double* rhs_hi, double* cost_lo,
+                     double* cost_hi) {
+    if (!T || !basis || !nonbasis || !rhs_lo || !rhs_hi || !cost_lo || !cost_hi || n < 1 ||
+        m < 1 || ld < (int64_t)m + 1 || (int64_t)n + m > INT32_MAX)
+        return -1;
+    host_ranging(T, ld, n, m, basis, nonbasis, rhs_lo, rhs_hi, cost_lo, cost_hi);
+    return 0;
 }
 
 // ---- native RCCL shard driver: the all-gather on the solver's own stream --------------------

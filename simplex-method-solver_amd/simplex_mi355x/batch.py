@@ -18,7 +18,10 @@ one by one -- still on the device.
 ``solve_batch_solutions`` (and ``solve_batch_arrays(solution=True)``) answer with every LP's whole
 solution -- all of x, the duals, the objective, the labels -- formed on the device by
 ``k_batch_solution`` (csrc/smx_solution.hpp) from the final tables and pivot logs; with
-``tables=False`` only that comes back, not the tables.
+``tables=False`` only that comes back, not the tables.  ``solve_batch_ranges`` (and
+``solve_batch_arrays(solution=True, ranging=True)``) add how far each constraint's constant and
+each cost can move before that final basis changes, formed on the device by ``k_batch_ranging``
+(csrc/smx_ranging.hpp) from the final tables and the labels.
 """
 from __future__ import annotations
 
@@ -28,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import MESSAGES, Error, Info, SimplexMethod, Solution
+from .engine import MESSAGES, Error, Info, Ranging, SimplexMethod, Solution
 
 # The wave kernel's envelope (k_batch): past it a launch goes to the workgroup kernel
 # (k_batch_wg), whose own envelope -- what one CU's LDS holds -- only the library states
@@ -74,6 +77,14 @@ def solution_lds_bytes(Rmax: int, ldb: int) -> int:
     if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
         return -1
     return int(_lib.load().smx_batch_solution_lds_bytes(int(Rmax), int(ldb)))
+
+
+def ranging_fits(Rmax: int, ldb: int) -> bool:
+    """Whether a launch of Rmax x ldb blocks is inside k_batch_ranging's envelope (the library is
+    the one source of the rule)."""
+    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
+        return False
+    return bool(_lib.load().smx_batch_ranging_fits(int(Rmax), int(ldb)))
 
 
 def _shape(cons, func):
@@ -172,7 +183,8 @@ def _fallback(cons, func, max_pivots, history):
 
 def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256,
                        history: bool = False, device=None, kernel: str = "auto",
-                       solution: bool = False, tables: bool = True) -> dict:
+                       solution: bool = False, tables: bool = True,
+                       ranging: bool = False) -> dict:
     """Array-level batch solve (no Python objects per problem).
 
     ``tabs``: float64 [B][Rmax][ldb], problem k in rows 0..n_k (f-row = row n_k), columns
@@ -195,9 +207,16 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
     ``basis`` [B][Rmax - 1] and ``nonbasis`` [B][ldb - 1] (-1 past n_k / m_k); see ``Solution``.
     ``tables=False`` (only with ``solution=True`` and without ``history``) leaves the final tables
     on the device: the result has no ``final``.
+
+    ``ranging=True`` (only with ``solution=True``, whose labels it consumes; with or without
+    ``tables``) adds what ``k_batch_ranging`` makes of every final table and those labels on the
+    device: ``rhs_lo``, ``rhs_hi`` [B][Rmax - 1] and ``cost_lo``, ``cost_hi`` [B][ldb - 1] (+0.0
+    past n_k / m_k); see ``Ranging``.
     """
     if not tables and not solution:
         raise ValueError("tables=False needs solution=True: nothing else would report the answer")
+    if ranging and not solution:
+        raise ValueError("ranging=True needs solution=True: the ranges are read off its labels")
     if not tables and history:
         raise ValueError("history=True needs the tables: tables=False cannot go with it")
     if not torch.cuda.is_available():
@@ -212,6 +231,8 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
               (dims[:, 1] < 1).any() or (dims[:, 0] < 1).any()):
         raise ValueError(ENVELOPE_ERROR)
     if solution and solution_lds_bytes(Rmax, ldb) < 0:
+        raise ValueError(ENVELOPE_ERROR)
+    if ranging and not ranging_fits(Rmax, ldb):
         raise ValueError(ENVELOPE_ERROR)
     P = int(max_pivots)
     L = _lib.load()
@@ -255,6 +276,17 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
                         "objective": d_obj.cpu().numpy(),
                         "basis": d_ba[:, :Rmax - 1].contiguous().cpu().numpy(),
                         "nonbasis": d_nb[:, :ldb - 1].contiguous().cpu().numpy()})
+        if ranging:
+            d_rl, d_rh = (torch.empty((B, Rmax), dtype=torch.float64, device=dev) for _ in "lh")
+            d_cl, d_ch = (torch.empty((B, ldb), dtype=torch.float64, device=dev) for _ in "lh")
+            _lib.check(L.smx_batch_ranging(
+                d_out.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, d_ba.data_ptr(),
+                d_nb.data_ptr(), d_rl.data_ptr(), d_rh.data_ptr(), d_cl.data_ptr(),
+                d_ch.data_ptr(), stream.cuda_stream), "smx_batch_ranging")
+            res.update({"rhs_lo": d_rl[:, :Rmax - 1].contiguous().cpu().numpy(),
+                        "rhs_hi": d_rh[:, :Rmax - 1].contiguous().cpu().numpy(),
+                        "cost_lo": d_cl[:, :ldb - 1].contiguous().cpu().numpy(),
+                        "cost_hi": d_ch[:, :ldb - 1].contiguous().cpu().numpy()})
         if history:
             steps = torch.arange(max(P, 1), device=dev)[None, :] < d_np[:, None]
             res["snaps"] = d_snaps[steps].cpu().numpy()
@@ -460,6 +492,59 @@ def solve_batch_solutions(problems, max_pivots: int = 256, device=None, kernel: 
             else:
                 raise RuntimeError(f"unexpected batch status {status}")
     return results, statuses
+
+
+def _fallback_ranging(cons, func, max_pivots):
+    try:
+        sm = SimplexMethod(cons, func)
+        sm.solve(record_history=False, max_pivots=max_pivots)
+        return sm.ranging(), sm.status
+    except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
+        return exc, "exception"
+
+
+def solve_batch_ranges(problems, max_pivots: int = 256, device=None, kernel: str = "auto"):
+    """Solve every ``(constraints, function)`` for the ranges of its final basis; returns
+    ``(ranges, statuses)``.
+
+    ``ranges[k]`` is the ``Ranging`` of problem k -- ``rhs_lo``, ``rhs_hi`` [n] and ``cost_lo``,
+    ``cost_hi`` [m] as numpy arrays -- equal to ``SimplexMethod(...).ranging()`` after
+    ``solve(record_history=False)``, or the ``IndexError`` the reference would raise;
+    ``statuses[k]`` as in ``solve_batch``.  The values stand whatever the status.  Routing and
+    launch splitting are ``solve_batch``'s; of a launch only the solutions and the ranges come
+    back from the device (``solve_batch_arrays(solution=True, ranging=True, tables=False)``)."""
+    problems = list(problems)
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
+    results = [None] * len(problems)
+    statuses = [None] * len(problems)
+    routes = _routes(problems, kernel)
+    for k, (c, f) in enumerate(problems):
+        if routes[k] == "single":
+            results[k], statuses[k] = _fallback_ranging(c, f, max_pivots)
+    P = int(max_pivots)
+    for which, idx in _launches(problems, routes, max_pivots, False):
+        tabs, dims = pack([problems[k] for k in idx])
+        out = solve_batch_arrays(tabs, dims, max_pivots, False, device, kernel=which,
+                                 solution=True, tables=False, ranging=True)
+        for q, k in enumerate(idx):
+            n, m = int(dims[q, 0]), int(dims[q, 1])
+            results[k] = Ranging(out["rhs_lo"][q, :n].copy(), out["rhs_hi"][q, :n].copy(),
+                                 out["cost_lo"][q, :m].copy(), out["cost_hi"][q, :m].copy())
+            statuses[k] = _status_name(int(out["status"][q]), int(out["npivots"][q]), P)
+    return results, statuses
+
+
+def _status_name(status, np_, P):
+    if status == _lib.OPTIMUM:
+        return "optimum"
+    if status in MESSAGES:
+        return "error"
+    if status == _lib.PIVOT and np_ >= P:
+        return "cap"
+    raise RuntimeError(f"unexpected batch status {status}")
 
 
 def _table(T, n, flen, m):

@@ -13,6 +13,7 @@ machine with an MI355X never takes it unless asked (``device="cpu"``).
 Additions (not in the reference, all opt-in): ``step()`` (one pick + pivot), ``solve()``
 (``get_solution`` with an optional pivot cap, or the chained no-history fast path),
 ``solution()`` (every variable, the duals and the objective of the current table),
+``ranging()`` (how far each constant and each cost can move before the basis changes),
 ``pivots`` / ``pivot_log`` and ``status``.
 
 Deliberate differences, all on inputs the reference UI never produces (main.py:309-312 always
@@ -49,6 +50,13 @@ MESSAGES = {_lib.INCORRECT: "incorrect system",                  # simplex.py:89
 # right; ``basis`` [n] / ``nonbasis`` [m]: the labels of the rows / columns; ``pivots``: how many
 # pivots led here.
 Solution = namedtuple("Solution", "x duals objective basis nonbasis pivots")
+
+# How far the data of one LP can move before its final basis changes (``SimplexMethod.ranging()``,
+# ``batch.solve_batch_ranges``): adding d to the constant t_i of constraint i keeps the basis for
+# ``rhs_lo[i] <= d <= rhs_hi[i]``, adding d to ``function[k]`` for ``cost_lo[k] <= d <=
+# cost_hi[k]``.  numpy float64 arrays of [n], [n], [m], [m]; the rules are stated once, in
+# include/smx.h (smx_batch_ranging).  At an optimum every lo <= 0 <= hi.
+Ranging = namedtuple("Ranging", "rhs_lo rhs_hi cost_lo cost_hi")
 
 
 def _label_code(label: str, m: int) -> int:
@@ -438,6 +446,29 @@ class SimplexMethod:
         for k in range(1, m):                                # summed strictly left to right
             objective = objective + self.function[k] * xs[k]
         return Solution(x, duals, float(objective), basis, nonbasis, self.pivots)
+
+    def ranging(self) -> Ranging:
+        """The current table's sensitivity ranges (``Ranging``): for which change of a
+        constraint's constant or of a cost the basis stays as it stands.  The labels come from
+        ``row`` / ``column``, the table from the backend's ``download()`` (the caller's own lists
+        before the first pivot), the rules from ``smx_host_ranging`` -- on every backend.  Values
+        are formed whatever ``status`` says; they mean something at an optimum."""
+        n, m = self.n, self.m
+        basis = np.array([_label_code(s, m) for s in self.column[:n]], dtype=np.int32)
+        nonbasis = np.array([_label_code(s, m) for s in self.row[:m]], dtype=np.int32)
+        if self._pristine:        # the caller's own lists; a short f-row reads as +0.0
+            T = np.zeros((n + 1, m + 1), dtype=np.float64)
+            T[:n] = self._initial[:n]
+            frow = self._initial[n][:m + 1]
+            T[n, :len(frow)] = frow
+        else:
+            T = np.ascontiguousarray(self._dev.download()[:n + 1, :m + 1], dtype=np.float64)
+        out = [np.empty(k, dtype=np.float64) for k in (n, n, m, m)]
+        err = _lib.load().smx_host_ranging(T.ctypes.data, T.shape[1], n, m, basis.ctypes.data,
+                                           nonbasis.ctypes.data, *(a.ctypes.data for a in out))
+        if err:
+            raise RuntimeError(f"smx_host_ranging refused n={n}, m={m} ({err})")
+        return Ranging(*out)
 
     # ---------------------------------------------------------------- the hot path -------
     def pick_element(self) -> (bool, int, int, float):
