@@ -289,6 +289,72 @@ int smx_host_ranging(const double* T, int64_t ld, int32_t n, int32_t m, const in
                      const int32_t* nonbasis, double* rhs_lo, double* rhs_hi, double* cost_lo,
                      double* cost_hi);
 
+/* ---- what-if scenarios: warm re-solves from a final table (smx_scenario.hpp) -----------------
+ * "The constants and costs of the ORIGINAL problem move; what is the optimum now?"  T is a final
+ * table ([n+1][m+1], f-row = row n, "-b" = column m) under the labels basis[p] / nonbasis[j] as
+ * smx_batch_solution writes them; T reads label(row p) = sum_j T[p][j] * label(col j) + T[p][m].
+ * A scenario is two dense vectors: drhs[i], i < n, is added to constraint i's constant t_i, and
+ * dcost[k], k < m, to function[k].  A delta that compares equal to zero (+0.0 or -0.0) contributes
+ * nothing and is skipped, so a zero delta can neither flip a -0.0 nor turn an inf of the table
+ * into NaN; a NaN delta is not equal to zero and is applied.  The scenario table S is T with row n
+ * and column m replaced, in two steps; every product is rounded on its own, every sum runs
+ * strictly in the stated order, there is no FMA:
+ *   1. costs -> f-row.  For every column j = 0..m (the constant column included):
+ *        v = T[n][j]
+ *        if j < m, nonbasis[j] = k < m and dcost[k] != 0:                v = v + dcost[k]
+ *        for p = 0..n-1 ascending: if basis[p] = k < m and dcost[k] != 0: v = v + dcost[k] * T[p][j]
+ *        S[n][j] = v
+ *   2. constants -> "-b" column.  For every row p = 0..n (the f-row included, reading step 1's
+ *      S[n][.]):
+ *        v = S[p][m]
+ *        if p < n, basis[p] = m + i and drhs[i] != 0:                       v = v + drhs[i]
+ *        for j = 0..m-1 ascending: if nonbasis[j] = m + i and drhs[i] != 0: v = v - S[p][j] * drhs[i]
+ *        S[p][m] = v
+ * Everything else in S is T's bits, the padding of an Rmax x ldb block included.  A label code
+ * outside 0..n+m-1 names nothing and is skipped.  func_s[k] = function[k] + dcost[k] (a zero delta
+ * skipped), +0.0 at k >= m: the scenario's own cost vector, on which its objective is formed.
+ * Values are formed whatever the base run's status: the table of a capped or failed run is still
+ * an equivalent form of its LP.  S is an equivalent form of the perturbed LP under T's labels, so
+ * the solve kernels carry on from it as from a fresh problem; the reference's selection rule is no
+ * dual simplex, though, and such a warm run need not terminate: a caller reads its
+ * status.
+ *
+ * smx_batch_scenario (device pointers, after smx_batch_solution): final fp64 [B][Rmax][ldb], dims
+ * int32 [B][3], basis int32 [B][Rmax], nonbasis int32 [B][ldb], func fp64 [B][ldb] (the original
+ * objective rows), drhs fp64 [B][S][Rmax], dcost fp64 [B][S][ldb] (entries past n_b / m_b are not
+ * read); outputs tabs_s fp64 [B*S][Rmax][ldb], func_s fp64 [B*S][ldb], dims_s int32 [B*S][3] (the
+ * dims of LP b); scenario q = b * S + s belongs to LP b.  A problem without 1 <= n_b < Rmax and
+ * 1 <= m_b < ldb gets T's block copied and func_s of +0.0.  Returns hipErrorInvalidValue (1)
+ * before any HIP call for B < 0, S < 0, B * S past 2^31 - 1, a shape outside
+ * smx_batch_scenario_fits or, with B * S > 0, a null pointer; B == 0 or S == 0 returns 0 without a
+ * launch. */
+int smx_batch_scenario(const double* final, const int32_t* dims, int32_t B, int32_t S,
+                       int32_t Rmax, int32_t ldb, const int32_t* basis, const int32_t* nonbasis,
+                       const double* func, const double* drhs, const double* dcost,
+                       double* tabs_s, double* func_s, int32_t* dims_s, void* stream);
+/* Host only: 1 inside the envelope (Rmax >= 2, ldb >= 2, Rmax + ldb <= 8192: every shape a batch
+ * kernel takes), else 0.  The single statement of it. */
+int smx_batch_scenario_fits(int32_t Rmax, int32_t ldb);
+/* The same rule on one HOST table with leading dimension ld >= m + 1 (synchronous): func, dcost
+ * [m], drhs [n]; S_out [n+1][ld_out] (ld_out >= m + 1; columns 0..m of every row are written; it
+ * must not overlap T) and func_out [m].  -1 for a null pointer, n < 1, m < 1, ld < m + 1 or
+ * ld_out < m + 1. */
+int smx_host_scenario(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                      const int32_t* nonbasis, const double* func, const double* drhs,
+                      const double* dcost, double* S_out, int64_t ld_out, double* func_out);
+/* smx_batch_solution from given start labels: LP q starts from basis0[q / group] (int32
+ * [..][Rmax]) and nonbasis0[q / group] (int32 [..][ldb]) instead of the identity -- the labels
+ * after a warm run on a scenario table are its base LP's final labels with the warm log applied
+ * (group = S).  Everything else is smx_batch_solution's contract.  An LP with a start code outside
+ * 0..n+m-1 at i < n_b or j < m_b gets the padding values only and objective +0.0; duplicate codes
+ * are the caller's error (the outputs are then unspecified, every access stays in bounds).
+ * group < 1 is refused like a bad shape. */
+int smx_batch_solution_from(const double* final, const int32_t* dims, int32_t B, int32_t Rmax,
+                            int32_t ldb, int32_t max_pivots, const int32_t* rc,
+                            const int32_t* npivots, const double* func, const int32_t* basis0,
+                            const int32_t* nonbasis0, int32_t group, double* x, double* duals,
+                            double* objective, int32_t* basis, int32_t* nonbasis, void* stream);
+
 /* ---- row-sharded engine (one process per GPU; exchange = caller's all-gather) ----------
  * Local tableau: shape->rows constraint rows (global rows row0 .. row0+rows-1) + a replica
  * of the f-row as local row `rows`.  Per pivot:

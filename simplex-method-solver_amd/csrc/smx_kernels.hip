@@ -15,6 +15,8 @@
 //                     objective and labels, one wavefront per LP)
 //   smx_ranging.hpp   k_batch_ranging (a batch's final tables and labels -> rhs and cost ranges,
 //                     one workgroup per LP) and host_ranging, its host twin
+//   smx_scenario.hpp  k_batch_scenario (a batch's final tables, labels and deltas -> the tables
+//                     warm re-solves start from, one workgroup per scenario) and host_scenario
 //   smx_resident.hpp  k_resident: the whole pivot loop in one persistent launch, tableau in LDS
 //   smx_block.hpp     k_blk_*: P pivots per HBM sweep, decisions planned from the sweep's input
 //   smx_sweep.hpp     k_blk_sweep, k_blk_sweep_rest: the sweep itself
@@ -63,6 +65,7 @@ static_assert(sizeof(smx_part) == 32, "smx_part layout");
 #include "smx_batch_gm.hpp"
 #include "smx_solution.hpp"
 #include "smx_ranging.hpp"
+#include "smx_scenario.hpp"
 #include "smx_resident.hpp"
 #include "smx_block.hpp"
 #include "smx_sweep.hpp"
@@ -1289,11 +1292,35 @@ int smx_batch_solution(const double* final, const int32_t* dims, int32_t B, int3
     if (!final || !dims || !rc || !npivots || !func || !x || !duals || !objective || !basis ||
         !nonbasis)
         return (int)hipErrorInvalidValue;
-    if (const int err = wg_raise_lds_limit<k_batch_solution>((int)(4 * kSolWaves * kSolMaxSum)))
+    if (const int err =
+            wg_raise_lds_limit<k_batch_solution<false>>((int)(4 * kSolWaves * kSolMaxSum)))
         return err;
-    hipLaunchKernelGGL(k_batch_solution, dim3((B + kSolWaves - 1) / kSolWaves),
+    hipLaunchKernelGGL(k_batch_solution<false>, dim3((B + kSolWaves - 1) / kSolWaves),
                        dim3(kSolWaves * kWave), (size_t)lds, S(stream), final, dims, B, Rmax, ldb,
-                       max_pivots, rc, npivots, func, x, duals, objective, basis, nonbasis);
+                       max_pivots, rc, npivots, func, x, duals, objective, basis, nonbasis,
+                       (const int32_t*)nullptr, (const int32_t*)nullptr, 1);
+    return (int)hipGetLastError();
+}
+
+// The same from given start labels: LP q starts from basis0 / nonbasis0 of LP q / group.
+int smx_batch_solution_from(const double* final, const int32_t* dims, int32_t B, int32_t Rmax,
+                            int32_t ldb, int32_t max_pivots, const int32_t* rc,
+                            const int32_t* npivots, const double* func, const int32_t* basis0,
+                            const int32_t* nonbasis0, int32_t group, double* x, double* duals,
+                            double* objective, int32_t* basis, int32_t* nonbasis, void* stream) {
+    const int64_t lds = sol_lds_bytes(Rmax, ldb);
+    if (!wg_args_ok(B, max_pivots) || lds < 0 || group < 1) return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    if (!final || !dims || !rc || !npivots || !func || !basis0 || !nonbasis0 || !x || !duals ||
+        !objective || !basis || !nonbasis)
+        return (int)hipErrorInvalidValue;
+    if (const int err =
+            wg_raise_lds_limit<k_batch_solution<true>>((int)(4 * kSolWaves * kSolMaxSum)))
+        return err;
+    hipLaunchKernelGGL(k_batch_solution<true>, dim3((B + kSolWaves - 1) / kSolWaves),
+                       dim3(kSolWaves * kWave), (size_t)lds, S(stream), final, dims, B, Rmax, ldb,
+                       max_pivots, rc, npivots, func, x, duals, objective, basis, nonbasis, basis0,
+                       nonbasis0, group);
     return (int)hipGetLastError();
 }
 
@@ -1320,6 +1347,36 @@ int smx_host_ranging(const double* T, int64_t ld, int32_t n, int32_t m, const in
         m < 1 || ld < (int64_t)m + 1 || (int64_t)n + m > INT32_MAX)
         return -1;
     host_ranging(T, ld, n, m, basis, nonbasis, rhs_lo, rhs_hi, cost_lo, cost_hi);
+    return 0;
+}
+
+// ---- what-if scenarios: the tables warm re-solves start from (smx_scenario.hpp) ----------------
+// The envelope is smx_batch_solution's (its labels are the input); the kernel holds no LDS.
+int smx_batch_scenario_fits(int32_t Rmax, int32_t ldb) { return sol_lds_bytes(Rmax, ldb) >= 0; }
+
+int smx_batch_scenario(const double* final, const int32_t* dims, int32_t B, int32_t S_,
+                       int32_t Rmax, int32_t ldb, const int32_t* basis, const int32_t* nonbasis,
+                       const double* func, const double* drhs, const double* dcost,
+                       double* tabs_s, double* func_s, int32_t* dims_s, void* stream) {
+    if (B < 0 || S_ < 0 || sol_lds_bytes(Rmax, ldb) < 0 || (int64_t)B * S_ > INT32_MAX)
+        return (int)hipErrorInvalidValue;
+    if (B == 0 || S_ == 0) return 0;
+    if (!final || !dims || !basis || !nonbasis || !func || !drhs || !dcost || !tabs_s || !func_s ||
+        !dims_s)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_batch_scenario, dim3((unsigned)(B * S_)), dim3(kScnBlock), 0, S(stream),
+                       final, dims, B, S_, Rmax, ldb, basis, nonbasis, func, drhs, dcost, tabs_s,
+                       func_s, dims_s);
+    return (int)hipGetLastError();
+}
+
+int smx_host_scenario(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                      const int32_t* nonbasis, const double* func, const double* drhs,
+                      const double* dcost, double* S_out, int64_t ld_out, double* func_out) {
+    if (!T || !basis || !nonbasis || !func || !drhs || !dcost || !S_out || !func_out || n < 1 ||
+        m < 1 || ld < (int64_t)m + 1 || ld_out < (int64_t)m + 1 || (int64_t)n + m > INT32_MAX)
+        return -1;
+    host_scenario(T, ld, n, m, basis, nonbasis, func, drhs, dcost, S_out, ld_out, func_out);
     return 0;
 }
 

@@ -41,11 +41,20 @@ __device__ __forceinline__ void sol_wave_sync() {
 // address, and every output element is written exactly once, as a gather.  No workgroup barrier:
 // a wave never reads what another wave wrote.  What a lane reads back from s_inv is range-checked
 // before it indexes the table.
+//
+// kFrom (smx_batch_solution_from): LP b starts from the labels basis0[b / group] / nonbasis0[b /
+// group] (as an earlier call wrote them) instead of the identity -- a warm run on a scenario table
+// carries on from its base LP's final labels.  Every start code is range-checked before it enters
+// LDS; an LP with a code outside 0..n+m-1 at i < n or j < m gets the padding values only (a wave
+// ballot decides it).  Duplicate codes are the caller's error: s_inv then holds a stale or a
+// contended entry, and what is read back from it is range-checked as always.
+template <bool kFrom>
 __global__ __launch_bounds__(kSolWaves * kWave) void k_batch_solution(
     const double* __restrict__ final, const int32_t* __restrict__ dims, int B, int Rmax, int ldb,
     int max_pivots, const int32_t* __restrict__ rc, const int32_t* __restrict__ npivots,
     const double* __restrict__ func, double* __restrict__ x, double* __restrict__ duals,
-    double* __restrict__ objective, int32_t* __restrict__ basis, int32_t* __restrict__ nonbasis) {
+    double* __restrict__ objective, int32_t* __restrict__ basis, int32_t* __restrict__ nonbasis,
+    const int32_t* __restrict__ basis0, const int32_t* __restrict__ nonbasis0, int group) {
     extern __shared__ uint16_t s_sol[];
     const int lane = threadIdx.x & (kWave - 1);
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // the LP's scalars: SGPRs
@@ -56,7 +65,7 @@ __global__ __launch_bounds__(kSolWaves * kWave) void k_batch_solution(
     double* db = duals + (size_t)b * Rmax;
     int32_t* bb = basis + (size_t)b * Rmax;
     int32_t* nb = nonbasis + (size_t)b * ldb;
-    if (n < 1 || m < 1 || n >= Rmax || m >= ldb) {
+    const auto padding = [&]() {
         for (int i = lane; i < Rmax; i += kWave) {
             db[i] = 0.0;
             bb[i] = -1;
@@ -66,13 +75,38 @@ __global__ __launch_bounds__(kSolWaves * kWave) void k_batch_solution(
             nb[j] = -1;
         }
         if (lane == 0) objective[b] = 0.0;
+    };
+    if (n < 1 || m < 1 || n >= Rmax || m >= ldb) {
+        padding();
         return;
     }
     uint16_t* s_basis = s_sol + (size_t)wid * 2 * (Rmax + ldb);
     uint16_t* s_nonb = s_basis + Rmax;
     uint16_t* s_inv = s_nonb + ldb;
-    for (int i = lane; i < n; i += kWave) s_basis[i] = (uint16_t)(m + i);
-    for (int j = lane; j < m; j += kWave) s_nonb[j] = (uint16_t)j;
+    if constexpr (kFrom) {
+        const int32_t* b0 = basis0 + (size_t)(b / group) * Rmax;
+        const int32_t* n0 = nonbasis0 + (size_t)(b / group) * ldb;
+        bool bad = false;
+        for (int i = lane; i < n; i += kWave) {
+            const int code = b0[i];
+            const bool ok = code >= 0 && code < n + m;
+            bad |= !ok;
+            s_basis[i] = (uint16_t)(ok ? code : 0);
+        }
+        for (int j = lane; j < m; j += kWave) {
+            const int code = n0[j];
+            const bool ok = code >= 0 && code < n + m;
+            bad |= !ok;
+            s_nonb[j] = (uint16_t)(ok ? code : 0);
+        }
+        if (__ballot(bad) != 0ull) {                 // the whole wave alike
+            padding();
+            return;
+        }
+    } else {
+        for (int i = lane; i < n; i += kWave) s_basis[i] = (uint16_t)(m + i);
+        for (int j = lane; j < m; j += kWave) s_nonb[j] = (uint16_t)j;
+    }
     sol_wave_sync();
     int np = npivots[b];
     np = np < 0 ? 0 : (np > max_pivots ? max_pivots : np);

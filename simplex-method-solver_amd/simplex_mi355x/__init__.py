@@ -9,7 +9,8 @@ from . import _lib
 
 _lib.load()  # no silent fallback: a missing/broken libsmx.so is an import error
 
-from .engine import Error, Info, Ranging, SimplexMethod, Solution  # noqa: E402
+from .engine import Error, Info, Ranging, Scenario, SimplexMethod, Solution  # noqa: E402
 from .device import DeviceTableau  # noqa: E402
 
-__all__ = ["SimplexMethod", "Info", "Error", "Solution", "Ranging", "DeviceTableau"]
+__all__ = ["SimplexMethod", "Info", "Error", "Solution", "Ranging", "Scenario",
+           "DeviceTableau"]

@@ -107,7 +107,9 @@ EXPORTS = (
     "smx_run", "smx_run_timed", "smx_graph_create", "smx_graph_launch", "smx_graph_destroy", "smx_update_forced",
     "smx_batch_solve", "smx_batch_solve_wg", "smx_batch_wg_lds_bytes", "smx_batch_solve_gm", "smx_batch_gm_fits", "smx_tune_batch_gm",
     "smx_batch_solution", "smx_batch_solution_lds_bytes",
-    "smx_batch_ranging", "smx_batch_ranging_fits", "smx_host_ranging", "smx_comm_unique_id", "smx_comm_init", "smx_comm_destroy",
+    "smx_batch_ranging", "smx_batch_ranging_fits", "smx_host_ranging",
+    "smx_batch_scenario", "smx_batch_scenario_fits", "smx_host_scenario", "smx_batch_solution_from",
+    "smx_comm_unique_id", "smx_comm_init", "smx_comm_destroy",
     "smx_shard_run", "smx_shard_run_timed", "smx_shard_pack", "smx_shard_merge", "smx_shard_update", "smx_shard_begin",
     "smx_shard_finish", "smx_shard_fused_prime", "smx_shard_fused_begin",
     "smx_shard_fused_finish", "smx_fused_publish", "smx_shard_ahead", "smx_shard_sweep",
@@ -190,6 +192,12 @@ def load():
         "smx_batch_ranging": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
         "smx_batch_ranging_fits": ([i32, i32], ctypes.c_int),
         "smx_host_ranging": ([vp, i64, i32, i32, vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        "smx_batch_scenario": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+                               ctypes.c_int),
+        "smx_batch_scenario_fits": ([i32, i32], ctypes.c_int),
+        "smx_host_scenario": ([vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp], ctypes.c_int),
+        "smx_batch_solution_from": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp,
+                                     vp, vp, vp, vp], ctypes.c_int),
         "smx_shard_begin": ([vp, sp, i32, vp, vp, vp, vp], ctypes.c_int),
         "smx_shard_finish": ([vp, vp, vp, i32, sp, i32, vp, vp, i64, vp, vp, vp], ctypes.c_int),
         "smx_shard_fused_prime": ([vp, sp, i32, vp, vp, vp], ctypes.c_int),

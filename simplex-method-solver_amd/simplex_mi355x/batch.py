@@ -22,6 +22,13 @@ solution -- all of x, the duals, the objective, the labels -- formed on the devi
 ``solve_batch_arrays(solution=True, ranging=True)``) add how far each constraint's constant and
 each cost can move before that final basis changes, formed on the device by ``k_batch_ranging``
 (csrc/smx_ranging.hpp) from the final tables and the labels.
+
+``solve_batch_scenarios`` (and ``solve_batch_scenarios_arrays``) answer "the constants and costs
+move: what is the optimum now?" without solving the perturbed problems from scratch:
+``k_batch_scenario`` (csrc/smx_scenario.hpp) re-expresses every scenario under its LP's final
+basis on the device, and the same solve kernel carries on from that table -- a handful of pivots
+where a cold solve takes hundreds.  Such a warm run need not terminate: every
+scenario reports its status, and the object-level call falls back to a cold solve.
 """
 from __future__ import annotations
 
@@ -31,7 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import MESSAGES, Error, Info, Ranging, SimplexMethod, Solution
+from .engine import MESSAGES, Error, Info, Ranging, Scenario, SimplexMethod, Solution
 
 # The wave kernel's envelope (k_batch): past it a launch goes to the workgroup kernel
 # (k_batch_wg), whose own envelope -- what one CU's LDS holds -- only the library states
@@ -85,6 +92,14 @@ def ranging_fits(Rmax: int, ldb: int) -> bool:
     if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
         return False
     return bool(_lib.load().smx_batch_ranging_fits(int(Rmax), int(ldb)))
+
+
+def scenario_fits(Rmax: int, ldb: int) -> bool:
+    """Whether a launch of Rmax x ldb blocks is inside k_batch_scenario's envelope (the library
+    is the one source of the rule)."""
+    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
+        return False
+    return bool(_lib.load().smx_batch_scenario_fits(int(Rmax), int(ldb)))
 
 
 def _shape(cons, func):
@@ -535,6 +550,290 @@ def solve_batch_ranges(problems, max_pivots: int = 256, device=None, kernel: str
                                  out["cost_lo"][q, :m].copy(), out["cost_hi"][q, :m].copy())
             statuses[k] = _status_name(int(out["status"][q]), int(out["npivots"][q]), P)
     return results, statuses
+
+
+def _device_solution(L, stream, dev, d_final, d_dims, B, Rmax, ldb, P, d_rc, d_np, d_func,
+                     start=None):
+    """Enqueue smx_batch_solution (``start`` = (basis0, nonbasis0, group): smx_batch_solution_from)
+    on fresh outputs; returns the device tensors (x, duals, objective, basis, nonbasis)."""
+    d_x = torch.empty((B, ldb), dtype=torch.float64, device=dev)
+    d_du = torch.empty((B, Rmax), dtype=torch.float64, device=dev)
+    d_obj = torch.empty(B, dtype=torch.float64, device=dev)
+    d_ba = torch.empty((B, Rmax), dtype=torch.int32, device=dev)
+    d_nb = torch.empty((B, ldb), dtype=torch.int32, device=dev)
+    head = (d_final.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, P, d_rc.data_ptr(),
+            d_np.data_ptr(), d_func.data_ptr())
+    tail = (d_x.data_ptr(), d_du.data_ptr(), d_obj.data_ptr(), d_ba.data_ptr(), d_nb.data_ptr(),
+            stream.cuda_stream)
+    if start is None:
+        _lib.check(L.smx_batch_solution(*head, *tail), "smx_batch_solution")
+    else:
+        _lib.check(L.smx_batch_solution_from(*head, start[0].data_ptr(), start[1].data_ptr(),
+                                             int(start[2]), *tail), "smx_batch_solution_from")
+    return d_x, d_du, d_obj, d_ba, d_nb
+
+
+def _device_ranging(L, stream, dev, d_final, d_dims, B, Rmax, ldb, d_ba, d_nb):
+    """Enqueue smx_batch_ranging on fresh outputs; returns (rhs_lo, rhs_hi, cost_lo, cost_hi)."""
+    d_rl, d_rh = (torch.empty((B, Rmax), dtype=torch.float64, device=dev) for _ in "lh")
+    d_cl, d_ch = (torch.empty((B, ldb), dtype=torch.float64, device=dev) for _ in "lh")
+    _lib.check(L.smx_batch_ranging(
+        d_final.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, d_ba.data_ptr(), d_nb.data_ptr(),
+        d_rl.data_ptr(), d_rh.data_ptr(), d_cl.data_ptr(), d_ch.data_ptr(), stream.cuda_stream),
+        "smx_batch_ranging")
+    return d_rl, d_rh, d_cl, d_ch
+
+
+def _solution_arrays(sol, Rmax, ldb, lead):
+    """The host arrays of a ``_device_solution`` result, cut like ``solve_batch_arrays`` cuts
+    them and reshaped to ``lead`` + [...]."""
+    d_x, d_du, d_obj, d_ba, d_nb = sol
+    return {"x": d_x[:, :ldb - 1].contiguous().cpu().numpy().reshape(*lead, ldb - 1),
+            "duals": d_du[:, :Rmax - 1].contiguous().cpu().numpy().reshape(*lead, Rmax - 1),
+            "objective": d_obj.cpu().numpy().reshape(*lead),
+            "basis": d_ba[:, :Rmax - 1].contiguous().cpu().numpy().reshape(*lead, Rmax - 1),
+            "nonbasis": d_nb[:, :ldb - 1].contiguous().cpu().numpy().reshape(*lead, ldb - 1)}
+
+
+def _ranging_arrays(rng, Rmax, ldb, lead):
+    d_rl, d_rh, d_cl, d_ch = rng
+    return {"rhs_lo": d_rl[:, :Rmax - 1].contiguous().cpu().numpy().reshape(*lead, Rmax - 1),
+            "rhs_hi": d_rh[:, :Rmax - 1].contiguous().cpu().numpy().reshape(*lead, Rmax - 1),
+            "cost_lo": d_cl[:, :ldb - 1].contiguous().cpu().numpy().reshape(*lead, ldb - 1),
+            "cost_hi": d_ch[:, :ldb - 1].contiguous().cpu().numpy().reshape(*lead, ldb - 1)}
+
+
+def solve_batch_scenarios_arrays(tabs: np.ndarray, dims: np.ndarray, drhs: np.ndarray,
+                                 dcost: np.ndarray, max_pivots: int = 256, warm_pivots=None,
+                                 device=None, kernel: str = "auto", ranging: bool = False) -> dict:
+    """Array-level what-if solve: every LP of ``tabs`` / ``dims`` (as in ``solve_batch_arrays``)
+    and S scenarios of each.  ``drhs``: float64 [B][S][Rmax - 1], ``drhs[k, s, i]`` is added to
+    the constant of constraint i of problem k; ``dcost``: float64 [B][S][ldb - 1], added to its
+    ``function``; entries past n_k / m_k are not read and a delta equal to zero is skipped.
+
+    One stream, no host round trip between the steps: the base solve, ``smx_batch_solution``
+    (``ranging``: ``smx_batch_ranging``), then ``smx_batch_scenario`` (the scenario tables under
+    every LP's final labels, include/smx.h), the warm solve of all B * S tables on the same kernel
+    capped at ``warm_pivots`` (default: ``max_pivots``), ``smx_batch_solution_from`` (the labels
+    carry on from the base LP's) and, with ``ranging``, ``smx_batch_ranging`` on the warm runs'
+    final tables.  The scenario tables are made in slices of S that keep them under
+    ``GM_TABLE_BUDGET``.
+
+    Returns ``base``: exactly the dict of ``solve_batch_arrays(solution=True, tables=False,
+    ranging=ranging)``; and per scenario, shaped [B][S]...: ``status``, ``npivots`` (the warm
+    pivots only), ``x``, ``duals``, ``objective`` (on the scenario's own costs), ``basis``,
+    ``nonbasis`` and with ``ranging`` the four range arrays.  A warm run need not terminate where
+    a cold solve of the perturbed problem would (the selection rule is no dual simplex): read
+    ``status``; SMX_PIVOT there means ``warm_pivots`` was reached."""
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    tabs = np.ascontiguousarray(tabs, dtype=np.float64)
+    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    drhs = np.ascontiguousarray(drhs, dtype=np.float64)
+    dcost = np.ascontiguousarray(dcost, dtype=np.float64)
+    B, Rmax, ldb = tabs.shape
+    if dims.shape != (B, 3):
+        raise ValueError("dims must be int32 [B][3]")
+    if drhs.ndim != 3 or drhs.shape[0] != B or drhs.shape[2] != Rmax - 1:
+        raise ValueError("drhs must be float64 [B][S][Rmax - 1]")
+    S = drhs.shape[1]
+    if dcost.shape != (B, S, ldb - 1):
+        raise ValueError("dcost must be float64 [B][S][ldb - 1]")
+    if not torch.cuda.is_available():
+        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
+    which = choose_kernel(Rmax, ldb, kernel) if B else "wave"
+    if B and ((dims[:, 0] + 1 > Rmax).any() or (dims[:, 1] + 1 > ldb).any() or
+              (dims[:, 1] < 1).any() or (dims[:, 0] < 1).any()):
+        raise ValueError(ENVELOPE_ERROR)
+    if solution_lds_bytes(Rmax, ldb) < 0 or not scenario_fits(Rmax, ldb):
+        raise ValueError(ENVELOPE_ERROR)
+    if ranging and not ranging_fits(Rmax, ldb):
+        raise ValueError(ENVELOPE_ERROR)
+    P = int(max_pivots)
+    Pw = P if warm_pivots is None else int(warm_pivots)
+    L = _lib.load()
+    solve, what = {"wave": (L.smx_batch_solve, "smx_batch_solve"),
+                   "workgroup": (L.smx_batch_solve_wg, "smx_batch_solve_wg"),
+                   "global": (L.smx_batch_solve_gm, "smx_batch_solve_gm")}[which]
+    # the deltas in the kernel's layout: rows of Rmax / ldb, the last entry unused
+    h_dr = np.zeros((B, S, Rmax), dtype=np.float64)
+    h_dr[:, :, :Rmax - 1] = drhs
+    h_dc = np.zeros((B, S, ldb), dtype=np.float64)
+    h_dc[:, :, :ldb - 1] = dcost
+    per = max(1, min(S, GM_TABLE_BUDGET // max(1, B * Rmax * ldb * 8)))
+    dev = torch.device(device if device is not None else "cuda")
+
+    def run(d_in, d_dims_, count, cap):
+        d_out = torch.empty_like(d_in)
+        d_rc = torch.zeros((count, max(cap, 1), 2), dtype=torch.int32, device=dev)
+        d_xv = torch.zeros((count, max(cap, 1), 2), dtype=torch.float64, device=dev)
+        d_st = torch.zeros(count, dtype=torch.int32, device=dev)
+        d_np = torch.zeros(count, dtype=torch.int32, device=dev)
+        _lib.check(solve(d_in.data_ptr(), d_dims_.data_ptr(), count, Rmax, ldb, cap,
+                         d_out.data_ptr(), d_rc.data_ptr(), d_xv.data_ptr(), None,
+                         d_st.data_ptr(), d_np.data_ptr(), stream.cuda_stream), what)
+        return d_out, d_rc, d_xv, d_st, d_np
+
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        d_tabs = torch.from_numpy(tabs).to(dev)
+        d_dims = torch.from_numpy(dims).to(dev)
+        d_dr = torch.from_numpy(h_dr).to(dev)
+        d_dc = torch.from_numpy(h_dc).to(dev)
+        d_out, d_rc, d_xv, d_st, d_np = run(d_tabs, d_dims, B, P)
+        d_func = d_tabs[torch.arange(B, device=dev), d_dims[:, 0].long()].contiguous()
+        sol = _device_solution(L, stream, dev, d_out, d_dims, B, Rmax, ldb, P, d_rc, d_np, d_func)
+        rng = (_device_ranging(L, stream, dev, d_out, d_dims, B, Rmax, ldb, sol[3], sol[4])
+               if ranging else None)
+        slices = []
+        for s0 in range(0, S, per):
+            c = min(S, s0 + per) - s0
+            Q = B * c
+            d_ts = torch.empty((Q, Rmax, ldb), dtype=torch.float64, device=dev)
+            d_fs = torch.empty((Q, ldb), dtype=torch.float64, device=dev)
+            d_ds = torch.empty((Q, 3), dtype=torch.int32, device=dev)
+            d_drs = d_dr[:, s0:s0 + c].contiguous()          # named: alive until the launch
+            d_dcs = d_dc[:, s0:s0 + c].contiguous()
+            _lib.check(L.smx_batch_scenario(
+                d_out.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, sol[3].data_ptr(),
+                sol[4].data_ptr(), d_func.data_ptr(), d_drs.data_ptr(), d_dcs.data_ptr(),
+                d_ts.data_ptr(), d_fs.data_ptr(), d_ds.data_ptr(), stream.cuda_stream),
+                "smx_batch_scenario")
+            d_wout, d_wrc, _, d_wst, d_wnp = run(d_ts, d_ds, Q, Pw)
+            wsol = _device_solution(L, stream, dev, d_wout, d_ds, Q, Rmax, ldb, Pw, d_wrc, d_wnp,
+                                    d_fs, start=(sol[3], sol[4], c))
+            wrng = (_device_ranging(L, stream, dev, d_wout, d_ds, Q, Rmax, ldb, wsol[3], wsol[4])
+                    if ranging else None)
+            slices.append((c, d_wst, d_wnp, wsol, wrng))
+            del d_ts, d_wout, d_wrc
+        # everything is enqueued: only now does anything come back
+        base = {"rc": d_rc.cpu().numpy(), "xv": d_xv.cpu().numpy(),
+                "status": d_st.cpu().numpy(), "npivots": d_np.cpu().numpy()}
+        base.update(_solution_arrays(sol, Rmax, ldb, (B,)))
+        if ranging:
+            base.update(_ranging_arrays(rng, Rmax, ldb, (B,)))
+        parts = []
+        for c, d_wst, d_wnp, wsol, wrng in slices:
+            part = {"status": d_wst.cpu().numpy().reshape(B, c),
+                    "npivots": d_wnp.cpu().numpy().reshape(B, c)}
+            part.update(_solution_arrays(wsol, Rmax, ldb, (B, c)))
+            if ranging:
+                part.update(_ranging_arrays(wrng, Rmax, ldb, (B, c)))
+            parts.append(part)
+    res = {"base": base}
+    if parts:
+        for key in parts[0]:
+            res[key] = np.concatenate([p[key] for p in parts], axis=1)
+    else:                                                    # S == 0
+        res.update({"status": np.zeros((B, 0), np.int32), "npivots": np.zeros((B, 0), np.int32),
+                    "x": np.zeros((B, 0, ldb - 1)), "duals": np.zeros((B, 0, Rmax - 1)),
+                    "objective": np.zeros((B, 0)),
+                    "basis": np.zeros((B, 0, Rmax - 1), np.int32),
+                    "nonbasis": np.zeros((B, 0, ldb - 1), np.int32)})
+        if ranging:
+            res.update({"rhs_lo": np.zeros((B, 0, Rmax - 1)), "rhs_hi": np.zeros((B, 0, Rmax - 1)),
+                        "cost_lo": np.zeros((B, 0, ldb - 1)), "cost_hi": np.zeros((B, 0, ldb - 1))})
+    return res
+
+
+def _perturbed(cons, func, drhs, dcost):
+    """The ORIGINAL problem with a scenario's deltas added (a delta equal to zero skipped)."""
+    cons = [list(r) for r in cons]
+    func = list(func)
+    if drhs is not None:
+        for i, d in enumerate(drhs):
+            if d != 0:
+                cons[i][-1] = cons[i][-1] + float(d)
+    if dcost is not None:
+        for k, d in enumerate(dcost):
+            if d != 0:
+                func[k] = func[k] + float(d)
+    return cons, func
+
+
+def _fallback_scenarios(cons, func, scen, max_pivots, warm_pivots):
+    try:
+        sm = SimplexMethod(cons, func)
+        sm.solve(record_history=False, max_pivots=max_pivots)
+        base = sm.solution()
+        out = []
+        for drhs, dcost in scen:
+            wi = sm.what_if(drhs, dcost)
+            wi.solve(record_history=False, max_pivots=warm_pivots)
+            out.append(Scenario(wi.solution(), wi.status, True))
+        return base, out
+    except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
+        return exc, [Scenario(exc, "exception", True) for _ in scen]
+
+
+def solve_batch_scenarios(problems, scenarios, max_pivots: int = 256, warm_pivots=None,
+                          cold_fallback: bool = True, device=None, kernel: str = "auto"):
+    """Solve every ``(constraints, function)`` and its what-if scenarios; ``scenarios[k]`` is a
+    list of ``(drhs, dcost)`` for problem k (``drhs`` [n] added to the constraints' constants,
+    ``dcost`` [m] to ``function``; either may be ``None``).  Returns per problem ``(Solution,
+    [Scenario])``: the base answer as ``solve_batch_solutions`` gives it and one ``Scenario`` per
+    entry of ``scenarios[k]``, in order.
+
+    Routing and launch grouping are ``solve_batch_solutions``'s; inside a launch the scenario
+    counts are padded with all-zero scenarios and dropped again
+    (``solve_batch_scenarios_arrays``).  Problems routed ``"single"`` go through
+    ``SimplexMethod.what_if``.  A warm run is capped at ``warm_pivots`` (default ``max_pivots``)
+    and need not terminate; with ``cold_fallback`` every scenario whose warm run did not end at
+    ``"optimum"`` is solved cold from the perturbed original through ``solve_batch_solutions``
+    with the full ``max_pivots`` and marked ``warm=False``."""
+    problems = list(problems)
+    scenarios = [list(s) for s in scenarios]
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    if len(scenarios) != len(problems):
+        raise ValueError("scenarios must hold one list of scenarios per problem")
+    if not torch.cuda.is_available():
+        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
+    P = int(max_pivots)
+    Pw = P if warm_pivots is None else int(warm_pivots)
+    results = [None] * len(problems)
+    routes = _routes(problems, kernel)
+    for k, (c, f) in enumerate(problems):
+        if routes[k] == "single":
+            results[k] = _fallback_scenarios(c, f, scenarios[k], P, Pw)
+    for which, idx in _launches(problems, routes, max_pivots, False):
+        tabs, dims = pack([problems[k] for k in idx])
+        _, Rmax, ldb = tabs.shape
+        S = max(len(scenarios[k]) for k in idx)
+        drhs = np.zeros((len(idx), S, Rmax - 1), dtype=np.float64)
+        dcost = np.zeros((len(idx), S, ldb - 1), dtype=np.float64)
+        for q, k in enumerate(idx):
+            n, m = int(dims[q, 0]), int(dims[q, 1])
+            for s, (dr, dc) in enumerate(scenarios[k]):
+                if dr is not None:
+                    drhs[q, s, :n] = np.asarray(dr, dtype=np.float64).reshape(n)
+                if dc is not None:
+                    dcost[q, s, :m] = np.asarray(dc, dtype=np.float64).reshape(m)
+        out = solve_batch_scenarios_arrays(tabs, dims, drhs, dcost, P, Pw, device, kernel=which)
+        base = out["base"]
+        for q, k in enumerate(idx):
+            n, m = int(dims[q, 0]), int(dims[q, 1])
+            sol = Solution(base["x"][q, :m].copy(), base["duals"][q, :n].copy(),
+                           float(base["objective"][q]), base["basis"][q, :n].copy(),
+                           base["nonbasis"][q, :m].copy(), int(base["npivots"][q]))
+            scen = []
+            for s in range(len(scenarios[k])):
+                np_ = int(out["npivots"][q, s])
+                scen.append(Scenario(
+                    Solution(out["x"][q, s, :m].copy(), out["duals"][q, s, :n].copy(),
+                             float(out["objective"][q, s]), out["basis"][q, s, :n].copy(),
+                             out["nonbasis"][q, s, :m].copy(), np_),
+                    _status_name(int(out["status"][q, s]), np_, Pw), True))
+            results[k] = (sol, scen)
+    if cold_fallback:
+        todo = [(k, s) for k, (_, scen) in enumerate(results) for s, sc in enumerate(scen)
+                if sc.status not in ("optimum", "exception")]
+        if todo:
+            cold = [_perturbed(*problems[k], *scenarios[k][s]) for k, s in todo]
+            sols, sts = solve_batch_solutions(cold, max_pivots, device, kernel)
+            for (k, s), sol, st in zip(todo, sols, sts):
+                results[k][1][s] = Scenario(sol, st, False)
+    return results
 
 
 def _status_name(status, np_, P):

@@ -59,6 +59,23 @@ Solution = namedtuple("Solution", "x duals objective basis nonbasis pivots")
 Ranging = namedtuple("Ranging", "rhs_lo rhs_hi cost_lo cost_hi")
 
 
+class Scenario:
+    """One what-if answer of ``batch.solve_batch_scenarios``: ``solution`` (a ``Solution``; its
+    objective is formed on the scenario's own costs, its ``pivots`` count the run that gave it),
+    ``status`` ("optimum", "error", "cap" or "exception") and ``warm`` -- True when the answer is
+    the warm run's from the base LP's final table, False when it is a cold solve of the perturbed
+    original."""
+    __slots__ = ("solution", "status", "warm")
+
+    def __init__(self, solution, status, warm):
+        self.solution = solution
+        self.status = status
+        self.warm = warm
+
+    def __repr__(self):
+        return f"Scenario(status={self.status!r}, warm={self.warm!r}, solution={self.solution!r})"
+
+
 def _label_code(label: str, m: int) -> int:
     return int(label[1:]) - 1 + (m if label[0] == 'y' else 0)
 
@@ -469,6 +486,69 @@ class SimplexMethod:
         if err:
             raise RuntimeError(f"smx_host_ranging refused n={n}, m={m} ({err})")
         return Ranging(*out)
+
+    def what_if(self, drhs=None, dcost=None) -> "SimplexMethod":
+        """A new ``SimplexMethod`` on the scenario table of the current one: ``drhs[i]`` added
+        to the constant of constraint i and ``dcost[k]`` to ``function[k]`` of the ORIGINAL
+        problem, re-expressed under the labels this table stands under (``None``: no change; a
+        delta equal to zero is skipped).  The labels come from ``row`` / ``column``, the table
+        from the backend's ``download()`` (the caller's own lists before the first pivot), the
+        rule from ``smx_host_scenario`` (include/smx.h) -- on every backend, so on a sharded or
+        16384 x 16384 tableau this is correct, not fast.  The result lives on the same backend:
+        its ``row`` / ``column`` carry the labels, its ``function`` is the scenario's cost vector,
+        its pivot log starts empty, and ``solve()``, ``solution()`` and ``ranging()`` carry on
+        from there.  Such a warm run need not terminate (the selection rule is no dual simplex):
+        cap it with ``max_pivots`` and read ``status``."""
+        n, m = self.n, self.m
+        basis = np.array([_label_code(s, m) for s in self.column[:n]], dtype=np.int32)
+        nonbasis = np.array([_label_code(s, m) for s in self.row[:m]], dtype=np.int32)
+        dr = np.zeros(n, dtype=np.float64)
+        dc = np.zeros(m, dtype=np.float64)
+        if drhs is not None:
+            dr[:] = np.asarray(drhs, dtype=np.float64).reshape(n)
+        if dcost is not None:
+            dc[:] = np.asarray(dcost, dtype=np.float64).reshape(m)
+        if self._pristine:        # the caller's own lists; a short f-row reads as +0.0
+            T = np.zeros((n + 1, m + 1), dtype=np.float64)
+            T[:n] = self._initial[:n]
+            frow = self._initial[n][:m + 1]
+            T[n, :len(frow)] = frow
+        else:
+            T = np.ascontiguousarray(self._dev.download()[:n + 1, :m + 1], dtype=np.float64)
+        func = np.zeros(m, dtype=np.float64)
+        k = min(len(self.function), m)
+        func[:k] = np.asarray(self.function[:k], dtype=np.float64)
+        S = np.empty((n + 1, m + 1), dtype=np.float64)
+        func_s = np.empty(m, dtype=np.float64)
+        err = _lib.load().smx_host_scenario(
+            T.ctypes.data, T.shape[1], n, m, basis.ctypes.data, nonbasis.ctypes.data,
+            func.ctypes.data, dr.ctypes.data, dc.ctypes.data, S.ctypes.data, S.shape[1],
+            func_s.ctypes.data)
+        if err:
+            raise RuntimeError(f"smx_host_scenario refused n={n}, m={m} ({err})")
+        cls = type(self)
+        new = cls.__new__(cls)
+        new.n, new.m, new.flen = n, m, self.flen
+        new.invalid_index = self.invalid_index
+        fs = func_s.tolist()
+        new.function = fs + [float(v) for v in self.function[m:]]
+        new.row, new.column = list(self.row), list(self.column)
+        new._initial = None
+        old = self._dev
+        if self.backend == "host":
+            new._dev = type(old)(S, n, m, self.flen)
+        elif self.backend == "sharded":
+            new._dev = type(old)(S, n, m, self.flen, old.devices, pivots=old.P,
+                                 exchange=old.exchange)
+        else:
+            new._dev = type(old)(S, n, m, self.flen, device=old.device)
+        new._pristine = False
+        new._int0 = new._int_hist = None
+        new.pivot_log = []
+        new.status = "ready"
+        new.cycle = None
+        new._tracker = None
+        return new
 
     # ---------------------------------------------------------------- the hot path -------
     def pick_element(self) -> (bool, int, int, float):
