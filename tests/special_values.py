@@ -9,6 +9,13 @@ members of classes 0 and 2, NaN < 0 is false in the "-b" and f-row scans, and th
 Random sprinkles of specials collapse to all-NaN tables within a few pivots, so every scenario is
 constructed; the census (numpy on the oracle's own tables) guards that each keeps producing the
 event it is for, and CONDITIONS / check_census hold what it must find.
+
+For the row-pair sweep layout (sweep form 7; test_gpu_block_pairs.py) the module also restates the
+sweep's grid and pairing (pair_geometry, wave_pairs) and counts, again on the oracle's tables
+alone, which pairs of a wave's rows take the pair fast path, which go row by row and which rows
+are odd tails (pair_census); PAIRS are the scenario cases run in that layout, PAIR_CONDITIONS /
+check_pair_census what the pair census must find on them and on the two constructed tables
+(fast_path_edge_table, mixed_pair_table).
 """
 from __future__ import annotations
 
@@ -294,11 +301,13 @@ def block_k(P: int) -> int:
 
 
 def census_cases():
-    """{(name, n, m, seed, k): "full" | "prefix" | "loose"} over everything the GPU file runs, at
-    both seeds."""
+    """{(name, n, m, seed, k): "full" | "prefix" | "loose"} over everything the GPU files run, at
+    both seeds (test_gpu_special_values.py, and PAIRS of test_gpu_block_pairs.py)."""
     out = {}
     for name, n, m, seed, k in chain_cases():
         out[name, n, m, seed, k] = "full"
+    for name, n, m, seed, P in PAIRS:
+        out.setdefault((name, n, m, seed, block_k(P)), "prefix")
     n, m, _ = CHAIN[0]
     for seed in SEEDS:
         for name in SCENARIOS:
@@ -312,3 +321,239 @@ def census_cases():
             for n_, m_, k in WAVE + WORKGROUP + WORKGROUP_MIXED + GLOBAL + [HOST]:
                 out[name, n_, m_, seed, k] = "loose" if (n_, m_) in LOOSE else "full"
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# The row-pair sweep layout (sweep form 7): which rows a wave pairs, and a census of the path each
+# pair takes.  test_gpu_block_pairs.py runs PAIRS and the two tables below with form 7 forced and
+# one sweep workgroup per CU; test_special_values_oracle.py checks PAIR_CONDITIONS on the CPU.
+def pair_chain(P: int) -> list:
+    """2 P + 3 pivots as three chained blocks: P (two pair phases past 12), P - 1 (the other
+    buffer parity) and a ragged block of 4."""
+    return [P, P - 1, 4]
+
+
+def edge_chain(P: int) -> list:
+    """4 P + 3 pivots as five chained blocks, both buffer parities."""
+    return [P, P - 1, P, P, 4]
+
+
+def mixed_pair_table(n: int, m: int, seed: int = 11) -> np.ndarray:
+    """A uniform table whose adjacent rows of a wave fall on different sweep paths: every third
+    constraint row scaled past 2^101 (inputs and multipliers out of the fast path's bounds),
+    exact zeros in every fifth column of every seventh row and negative zeros in every fifth
+    column of every eleventh (a zero multiplier where such a column is a block's first pivot's).
+
+    What the pair census finds on it: a third of the rows being scaled, a block of 13 pivots or
+    more all but surely has one of them as a pivot row, whose values past 2^101 leave no chunk
+    free and nearly every row with an unbounded multiplier (flag 0): in such a block every pair
+    goes row by row through the window-tracked and exact paths.  Only a short block can be free;
+    MIXED_PAIR_SEEDS are seeds at which the ragged block of 4 after 20 + 19 and after 24 + 23
+    pivots is, with flag-1 rows paired with the scaled ones, so those runs hold fast pairs and
+    mixed pairs as well.  (The pair fast path next to its fallback in blocks of 13, 20 and 24
+    pivots is what PAIRS and fast_path_edge_table are for.)"""
+    from simplex_mi355x import lp
+    T = lp.dense_tableau("uniform", seed, n, m)
+    T[0:n:3] *= 2.0 ** 102
+    T[1:n:7, 0:m:5] = 0.0
+    T[2:n:11, 0:m:5] = -0.0
+    return T
+
+
+# shape -> seed of mixed_pair_table for the runs at 20 and 24 pivots per sweep (the first seeds
+# from 11 on at which PAIR_CONDITIONS["tables"] holds for both; seed 11 itself, the run at 13
+# pivots per sweep, has no free chunk in any of its three blocks)
+MIXED_PAIR_SEEDS = {(1000, 1023): 16, (1000, 1100): 25}
+
+
+def fast_path_edge_table(n: int, m: int) -> np.ndarray:
+    """The sweep's unchecked fast path next to its fallbacks in one table (n >= 900, m >= 701):
+    rows scaled past 2^101 (input bound), rows scaled to ~2^-60 (small numerators), columns scaled
+    to ~2^-99 (pivot-row values below 2^-100: the chunk falls back), exact zeros (zero multipliers
+    and pivot-row values), signed zeros."""
+    from simplex_mi355x import lp
+    T = lp.dense_tableau("uniform", 5, n, m)
+    T[0:40] *= 2.0 ** 102
+    T[40:90] *= 2.0 ** -60
+    T[:, 200:260] *= 2.0 ** -99
+    T[300:340, 500:540] = 0.0
+    T[340:350, 600:640] = -0.0
+    T[500:900, 700] = 0.0
+    return T
+
+
+def pair_geometry(R: int, C: int, cus: int, bpc: int = 1):
+    """(nchunks, qs) of the LDS sweep layouts on a table of R rows (the f-row included) and C
+    columns with bpc workgroups per CU on cus CUs: sweep_grid_lds (smx_kernels.hip:716-723) and
+    blk_geom_wg (smx_sweep.hpp:337-340) restated.  The grid is per * nchunks workgroups of four
+    waves; workgroup b sweeps chunk b % nchunks, and its wave w starts at row
+    base = (b // nchunks) * 4 + w < qs = 4 * per and takes rows base, base + qs, ... < R."""
+    nchunks = -(-C // 128)
+    per = min(max(cus * bpc // nchunks, 1), -(-R // 4))
+    return nchunks, 4 * per
+
+
+def wave_pairs(R: int, qs: int):
+    """([(a, b)], [odd]) over every wave of one chunk: blk_row_pairs (smx_sweep.hpp:303-323) takes
+    a wave's rows two at a time, (base + 2 t qs, base + (2 t + 1) qs); a last row whose partner
+    would be past R is the odd tail (`two` false in pairf, smx_sweep.hpp:529-531), swept alone."""
+    pairs, odd = [], []
+    for base in range(min(qs, R)):
+        rows = list(range(base, R, qs))
+        pairs += [(rows[t], rows[t + 1]) for t in range(0, len(rows) - 1, 2)]
+        if len(rows) % 2:
+            odd.append(rows[-1])
+    return pairs, odd
+
+
+def _bounded(v):
+    """|v| in [2^-100, 2^101): bnd_term(v) < kBndSpan (smx_block.hpp:208-213); NaN, inf, zeros and
+    denormals are outside."""
+    with np.errstate(invalid="ignore"):
+        a = np.abs(v)
+        return (a >= LO) & (a < HI)
+
+
+PAIR_COUNTS = ("both", "one", "neither", "odd_fast", "odd_slow", "free_chunks", "vote_a", "vote_b",
+               "both_phase2")
+
+
+def pair_census(T: np.ndarray, n: int, m: int, blocks, cus: int, bpc: int = 1) -> dict:
+    """The path every row pair of the form-7 sweep takes over the chained blocks `blocks` (pivots
+    per block), from the oracle's tables alone (c_oracle.pick / c_oracle.pivot, numpy).
+
+    Per block starting at pivot k, with (r_q, c_q) the oracle's pivots: the multipliers
+    mul[i][q] = T_{k+q}[i][c_q], the pivot rows' values T_{k+q}[r_q][.], the elements
+    e_q = T_{k+q}[r_q][c_q] and the block's input table T_k.  From these, as the kernels decide:
+
+    row flag    blk_rflag (smx_block.hpp:136-162; written by each planner's last step): 2 for a
+                pivot row of the block, else 1 if every multiplier is bounded, else 3 if every one
+                is bounded or +-0 (at least one is +-0), else 0.  Every row of the table, the f-row
+                (row n) too: the sweep treats it like any other.
+    chunk free  chunk_flags (smx_sweep.hpp:410-430): every e_q bounded (then h->ok[q] holds as
+                well: the division window is the wider one), and every pivot-row value in the
+                chunk's columns below C = m + 1.
+    unit fast   a (row, chunk) unit: the chunk free, the flag 1, and every input of the row in the
+                chunk finite with |x| < 2^101 (xt < kBndXMax: rowf's vote, smx_sweep.hpp:457-468).
+    pair fast   pairf (smx_sweep.hpp:526-589): both rows' flags 1 and ONE vote over the four
+                inputs of a lane (:537-541), that is, both units fast.  Any other pair goes row by
+                row through rowf (:585-587), and so does an odd tail.
+    (A last chunk of odd width also loads the row's padding element: zero in every unit that is
+    otherwise fast, so it is left out here.)
+
+    Returns the counts PAIR_COUNTS summed over the blocks -- (pair, chunk) units with both rows
+    fast, exactly one, neither; odd tails fast and not; free chunks; pairs in a free chunk with
+    both flags 1 whose vote fails on row a's inputs alone (vote_a) or row b's (vote_b); pairs with
+    both rows fast in blocks of more than 12 pivots (both_phase2) -- and "blocks" (the same per
+    block, with the block's pivot rows, row flags and the unit mask `fast` [R, nchunks]), "pairs"
+    and "odd" (wave_pairs), "status", "done", "nan_share" and "final" as census() has them."""
+    from oracle import c_oracle
+    R, C = n + 1, m + 1
+    nchunks, qs = pair_geometry(R, C, cus, bpc)
+    pairs, odd = wave_pairs(R, qs)
+    pa = np.array([p[0] for p in pairs], dtype=np.int64)
+    pb = np.array([p[1] for p in pairs], dtype=np.int64)
+    od = np.array(odd, dtype=np.int64)
+    cur = np.ascontiguousarray(T, dtype=np.float64).copy()
+    out = dict({a: 0 for a in PAIR_COUNTS}, blocks=[], pairs=pairs, odd=odd, status=0, done=0,
+               geometry=(nchunks, qs))
+    for Pb in blocks:
+        Tin = cur
+        mul, prow, e, prows = np.empty((R, Pb)), np.empty((Pb, C)), np.empty(Pb), []
+        for q in range(Pb):
+            st, r, c = c_oracle.pick(cur, n, m, m)
+            if st != 0:
+                out["status"] = st
+                break
+            mul[:, q], prow[q], e[q] = cur[:, c], cur[r, :C], cur[r, c]
+            prows.append(int(r))
+            cur = c_oracle.pivot(cur, r, c, threads=8)
+            out["done"] += 1
+        if out["status"] != 0:
+            break
+        bnd = _bounded(mul)
+        flag = np.where(bnd.all(axis=1), 1, np.where((bnd | (mul == 0)).all(axis=1), 3, 0))
+        flag[prows] = 2
+        free = np.array([_bounded(e).all() and _bounded(prow[:, ch * 128:(ch + 1) * 128]).all()
+                         for ch in range(nchunks)])
+        with np.errstate(invalid="ignore"):
+            xok = np.stack([(np.abs(Tin[:, ch * 128:min((ch + 1) * 128, C)]) < HI).all(axis=1)
+                            for ch in range(nchunks)], axis=1)
+        fast = xok & free[None, :] & (flag == 1)[:, None]
+        fa, fb, fo = fast[pa], fast[pb], fast[od]
+        # pairs that only the vote keeps off the fast path (chunk free, both flags 1), by the row
+        # whose input fails it
+        votes = (free[None, :] & ((flag[pa] == 1) & (flag[pb] == 1))[:, None])
+        blk = dict(both=int((fa & fb).sum()), one=int((fa ^ fb).sum()),
+                   neither=int((~fa & ~fb).sum()), odd_fast=int(fo.sum()),
+                   odd_slow=int((~fo).sum()), free_chunks=int(free.sum()),
+                   vote_a=int((votes & ~xok[pa] & xok[pb]).sum()),
+                   vote_b=int((votes & xok[pa] & ~xok[pb]).sum()),
+                   both_phase2=int((fa & fb).sum()) if Pb > 12 else 0,
+                   pivot_rows=prows, flags=flag, fast=fast)
+        for a in PAIR_COUNTS:
+            out[a] += blk[a]
+        out["blocks"].append(blk)
+    body = np.concatenate([cur[:n].ravel(), cur[n, :m]])
+    out["nan_share"] = float(np.isnan(body).mean())
+    out["final"] = cur
+    return out
+
+
+# (scenario, n, m, seed, pivots per sweep): every scenario at 700 x 900 (701 rows: with a row
+# stride of 128 most waves own 5 rows, two pairs and an odd tail; 901 columns: a ragged last chunk
+# of 5) at 13 (12 + 1) and 24 (12 + 12) pivots per sweep, and the three scenarios that keep the pair
+# fast path next to its fallback at 1023 x 1023 (exactly 8 rows per wave, no tails) at 20 (12 + 8).
+# sprinkle at 700 x 900 with seed 6 is here, though SKIP keeps it from the full lists: the prefix
+# conditions hold for it.
+SHARP = ("inf_b", "nan_later", "sprinkle")
+PAIRS = [(name, 700, 900, seed, P) for name in SCENARIOS for P in (13, 24) for seed in SEEDS] + \
+        [(name, 1023, 1023, seed, 20) for name in SHARP for seed in SEEDS]
+
+# What the pair census must find with one sweep workgroup per CU, summed over the run's three
+# blocks -- conditions that keep the GPU comparisons from going blind, not measurements (those
+# are far above: the smallest counts measured at 256 CUs are in test_gpu_block_pairs.py's
+# docstring).  Every case besides: status "cap", all pivots done.
+PAIR_CONDITIONS = {
+    "sharp": ">= 1000 (pair, chunk) units with both rows fast and >= 100 with exactly one "
+             "(inf_b, nan_later, sprinkle: the pair fast path and its row-by-row fallback side by "
+             "side); of the mixed ones at least one that only the vote holds back through row a's "
+             "inputs and one through row b's (chunk free, both flags 1: a vote over one row alone "
+             "would take it), and at least one fast pair in a block of more than 12 pivots (a "
+             "second phase reading the wrong row's multipliers would change it)",
+    "fallback": "no pair with both rows fast (nan_first, cols150, rows150: every pair goes row by "
+                "row through the prefetch rotation)",
+    "tails": "at 700 x 900 at least one odd tail in each class that occurs: fast and not for the "
+             "sharp scenarios, not fast for the others",
+    "tables": "fast_path_edge_table and mixed_pair_table: at least one unit of each pair class "
+              "(both fast, exactly one) and of each odd-tail class where the shape has tails",
+}
+
+
+def check_pair_census(name: str, n: int, m: int, k: int, cen: dict) -> None:
+    """Assert PAIR_CONDITIONS on a pair census of k pivots (name: a scenario, or "table" for the
+    two constructed tables)."""
+    what = (name, n, m, k, cen["geometry"], {a: cen[a] for a in PAIR_COUNTS})
+    assert cen["status"] == 0 and cen["done"] == k, what
+    tails = len(cen["odd"]) > 0
+    if name == "table":
+        assert cen["both"] >= 1 and cen["one"] >= 1, what
+        if tails:
+            assert cen["odd_fast"] >= 1 and cen["odd_slow"] >= 1, what
+    elif name in SHARP:
+        assert cen["both"] >= 1000 and cen["one"] >= 100, what
+        assert min(cen["vote_a"], cen["vote_b"], cen["both_phase2"]) >= 1, what
+        if (n, m) == (700, 900):
+            assert cen["odd_fast"] >= 1 and cen["odd_slow"] >= 1, what
+    elif name in SCENARIOS:
+        assert cen["both"] == 0, what
+        if (n, m) == (700, 900):
+            assert cen["odd_slow"] >= 1, what
+    else:
+        raise ValueError(name)
+
+
+@functools.lru_cache(maxsize=None)
+def pair_case_census(name: str, n: int, m: int, seed: int, P: int, cus: int) -> dict:
+    """pair_census of a PAIRS case over pair_chain(P), computed once per CU count."""
+    return pair_census(scenario(name, n, m, seed), n, m, pair_chain(P), cus)

@@ -196,20 +196,16 @@ def test_block_bounded_fast_path_edges_vs_oracle(block_mode, sweep_form, P, form
     """The one-row sweep's unchecked fast path (smx_sweep.hpp; the bounds: smx_block.hpp, kBndSpan) next to its fallbacks in
     one table: rows scaled past 2^101 (input bound), rows scaled to ~2^-60 (small numerators),
     columns scaled to ~2^-99 (pivot-row values below 2^-100: the chunk falls back), exact zeros
-    (zero multipliers and pivot-row values), signed zeros -- bit-exact against the C oracle."""
+    (zero multipliers and pivot-row values), signed zeros -- bit-exact against the C oracle.  (The
+    table is special_values.fast_path_edge_table; test_gpu_block_pairs.py runs it in the row-pair
+    layout, form 7, with a grid that gives a wave real pairs.)"""
     from oracle import c_oracle
-    from simplex_mi355x import lp
+    from special_values import fast_path_edge_table
     import simplex
     sweep_form(form)
     block_mode(P)
     n = m = 1023
-    T = lp.dense_tableau("uniform", 5, n, m)
-    T[0:40] *= 2.0 ** 102
-    T[40:90] *= 2.0 ** -60
-    T[:, 200:260] *= 2.0 ** -99
-    T[300:340, 500:540] = 0.0
-    T[340:350, 600:640] = -0.0
-    T[500:900, 700] = 0.0
+    T = fast_path_edge_table(n, m)
     sm = simplex.SimplexMethod(T[:n].tolist(), T[n, :m].tolist())
     assert sm._dev.block_plan()[1] == P
     k = 4 * P + 3

@@ -9,6 +9,38 @@ trajectory fixtures (tiny tables: the single-row tail only).
 Small tables give a wave fewer than two rows under the default grid of 8 workgroups per CU, so the
 oracle cases run the sweep with one workgroup per CU (smx_tune_set(-2, 1)): at n = 1000 rows and
 8 or 9 column chunks a wave then owns 7-9 rows.
+
+What exists only in the pair layout -- the one vote over a pair's four inputs, the odd last row,
+the second phase's reload of both rows' multipliers, the row-by-row fallback run from inside the
+pair loop's prefetch rotation -- also sees NaN, inf, denormals and 2^+-150 values here, with real
+pairs, at 13, 20 and 24 pivots per sweep:
+  * special_values.PAIRS, every planner: inf_b, nan_later and sprinkle put fast pairs and pairs
+    with exactly one fast row side by side; nan_first, cols150 and rows150 send every pair row by
+    row.  700 x 900 gives most waves two pairs and an odd tail and a ragged last chunk, 1023^2
+    exactly four pairs per wave.
+  * the fast-path edge table of test_gpu_block.py (rows past 2^101 and at 2^-60, columns at
+    2^-99, zero and -0 blocks) at 1023^2 and 1000 x 1100, 4 P + 3 pivots;
+  * mixed_pair_table at 20 and 24 pivots per sweep, and on two simulated ranks;
+  * sprinkle under forms 5, 6 and 7.
+Which path each pair takes is counted on the CPU by special_values.pair_census, and every test
+that relies on a mix first checks PAIR_CONDITIONS at the device's own CU count, so a geometry that
+moved fails by name.  At 256 CUs the census finds, as (both rows fast, exactly one, neither)
+(pair, chunk) units summed over a run, seeds 5 / 6:
+  nan_first, cols150, rows150  700 x 900  P = 13 and 24   0, 0, 7608 throughout
+  nan_later  700 x 900   P = 13   3704, 1109, 2795 / 3650, 1105, 2853
+                         P = 24   3698, 1121, 2789 / 3635, 1111, 2862
+  inf_b      700 x 900   P = 13   7141, 417, 50 / 7198, 362, 48
+                         P = 24   7082, 471, 55 / 7135, 424, 49
+  sprinkle   700 x 900   P = 13   1992, 215, 5401 / 6280, 987, 341
+                         P = 24   1708, 184, 5716 / 5982, 965, 661
+  inf_b      1023^2      P = 20   11551, 668, 69 / 11608, 606, 74
+  nan_later  1023^2      P = 20   4598, 1530, 6160 / 6068, 2613, 3607
+  sprinkle   1023^2      P = 20   2551, 503, 9234 / 4350, 737, 7201
+(700 x 900: 1608 odd-tail units per run, 46 to 1227 of them not fast in the sharp scenarios.)
+Of the mixed units of the nine sharp lines, 24 to 442 per run are held off the fast path by the
+vote alone through row a's inputs and 42 to 394 through row b's (a vote over one row would take
+them), and 756 to 7702 fast pairs lie in blocks of more than 12 pivots (a second phase reading the
+other row's multipliers would change them): PAIR_CONDITIONS asks for at least one of each.
 """
 from __future__ import annotations
 
@@ -17,6 +49,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import special_values as sv
 from golden_util import trajectory_cap, trajectory_cases
 
 pytestmark = pytest.mark.gpu
@@ -62,10 +95,19 @@ def small_grid():
     _lib.check(lib.smx_tune_set(-2, prev.value), "smx_tune_set")
 
 
+@pytest.fixture
+def planner():
+    """Set smx_tune_block_planner (planner, window slots) for one test."""
+    from simplex_mi355x import _lib
+    prev = _lib.tune_block_planner(-1, -1)
+    yield _lib.tune_block_planner
+    _lib.tune_block_planner(prev, 0)
+
+
 def _chunks(P):
     """2 P + 3 pivots in three chains of one block each: P (two phases past 12), P - 1 (the other
     parity: one of the two is in place, the other out of place) and a ragged last block of 4."""
-    return [P, P - 1, 4]
+    return sv.pair_chain(P)
 
 
 def _run_vs_oracle(T, n, m, P):
@@ -104,16 +146,8 @@ def test_pairs_vs_oracle(block_mode, sweep_form, small_grid, n, m, P, kind):
 
 
 def mixed_pair_table(n, m):
-    """A uniform table whose adjacent rows of a wave fall on different sweep paths: every third
-    constraint row scaled past 2^101 (inputs and multipliers out of the fast path's bounds),
-    exact zeros in every fifth column of every seventh row and negative zeros in every fifth
-    column of every eleventh (zero multipliers wherever such a column is a pivot's: flag-3 rows)."""
-    from simplex_mi355x import lp
-    T = lp.dense_tableau("uniform", SEED, n, m)
-    T[0:n:3] *= 2.0 ** 102
-    T[1:n:7, 0:m:5] = 0.0
-    T[2:n:11, 0:m:5] = -0.0
-    return T
+    """special_values.mixed_pair_table at this file's seed."""
+    return sv.mixed_pair_table(n, m, SEED)
 
 
 def test_mixed_pairs_vs_oracle(block_mode, sweep_form, small_grid):
@@ -208,3 +242,140 @@ def test_every_fixture_form7(block_mode, sweep_form):
         if rec["outcome"]["kind"] in ("optimum", "error"):
             assert res[0][3] == rec["steps"][-1]["hash"], label
     assert n_blk > 250
+
+
+# ----------------------------------------------------------------------------------------------
+# NaN, inf, extreme exponents and the fast path's edges with real pairs
+def _cus():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _device_chain(T, n, m, P, blocks):
+    """The blocks as one run / sync_state each on a DeviceTableau (one sweep per call, both
+    buffer parities over the chain): (device, last control block)."""
+    from simplex_mi355x.device import DeviceTableau
+    dev = DeviceTableau(T, n, m, m)
+    assert dev.block_plan()[1] == P
+    ctl = None
+    for c in blocks:
+        assert c <= P
+        dev.run(c, graph=False)
+        ctl = dev.sync_state()
+    return dev, ctl
+
+
+PAIR_IDS = ["{}-{}x{}-s{}-P{}".format(*c) for c in sv.PAIRS]
+
+
+@pytest.mark.parametrize("plan", [0, 2, 1], ids=["wplan", "wstep", "register"])
+@pytest.mark.parametrize("name,n,m,seed,P", sv.PAIRS, ids=PAIR_IDS)
+def test_pairs_special_values_vs_oracle(block_mode, sweep_form, small_grid, planner, name, n, m,
+                                        seed, P, plan):
+    """special_values.PAIRS in the pair layout, the row flags written by each planner: pivot log,
+    pivot count and status exactly, the table under same_bits_or_nan.  PAIR_CONDITIONS first, at
+    this device's CU count."""
+    k = sv.block_k(P)
+    sv.check_pair_census(name, n, m, k, sv.pair_case_census(name, n, m, seed, P, _cus()))
+    sweep_form(7)
+    block_mode(P)
+    planner(plan, 0)
+    _, Tref, st, done, log = sv.reference(name, n, m, seed, k)
+    dev, ctl = _device_chain(sv.scenario(name, n, m, seed), n, m, P, sv.pair_chain(P))
+    what = (name, n, m, seed, P, plan)
+    assert int(ctl["npivots"]) == done == k, what
+    assert np.array_equal(dev.read_log(0, done), log), what
+    assert bool(ctl["term"]) == (st != 0), what
+    sv.same_table_as_oracle(dev.download(), Tref, n, m, what)
+    dev.close()
+
+
+def _table_vs_oracle(T, n, m, P, blocks):
+    """A finite table through the chained blocks against the C oracle: log and int64 bits, after
+    PAIR_CONDITIONS["tables"] at this device's CU count."""
+    from oracle import c_oracle
+    k = sum(blocks)
+    sv.check_pair_census("table", n, m, k, sv.pair_census(T, n, m, blocks, _cus()))
+    Tref, st, done, log = c_oracle.run(T, n, m, m, k, threads=8)
+    assert (st, done) == (0, k)
+    dev, ctl = _device_chain(T, n, m, P, blocks)
+    assert int(ctl["npivots"]) == done and not ctl["term"]
+    assert np.array_equal(dev.read_log(0, done), log)
+    got = dev.download()
+    dev.close()
+    assert np.array_equal(got[:n].view(np.int64), Tref[:n].view(np.int64)), \
+        sv.first_difference(got[:n], Tref[:n])
+    assert np.array_equal(got[n, :m].view(np.int64), Tref[n, :m].view(np.int64))
+
+
+@pytest.mark.parametrize("P", [13, 20, 24])
+@pytest.mark.parametrize("n,m", [(1023, 1023), (1000, 1100)])
+def test_pairs_fast_path_edges_vs_oracle(block_mode, sweep_form, small_grid, n, m, P):
+    """test_gpu_block.py's fast-path edge table with pairs (1023^2: four pairs per wave;
+    1000 x 1100: odd tails and a ragged ninth chunk), 4 P + 3 pivots in five blocks."""
+    sweep_form(7)
+    block_mode(P)
+    _table_vs_oracle(sv.fast_path_edge_table(n, m), n, m, P, sv.edge_chain(P))
+
+
+@pytest.mark.parametrize("P", [20, 24])
+@pytest.mark.parametrize("n,m", sorted(sv.MIXED_PAIR_SEEDS))
+def test_mixed_pairs_past_one_phase_vs_oracle(block_mode, sweep_form, small_grid, n, m, P):
+    """mixed_pair_table with a second pair phase of 8 and of 12 pivots (at the seeds of
+    special_values.MIXED_PAIR_SEEDS, where the run holds fast and mixed pairs as well as its
+    all-fallback blocks)."""
+    sweep_form(7)
+    block_mode(P)
+    T = sv.mixed_pair_table(n, m, sv.MIXED_PAIR_SEEDS[n, m])
+    _table_vs_oracle(T, n, m, P, sv.pair_chain(P))
+
+
+def test_forms_agree_on_special_values(block_mode, sweep_form, small_grid):
+    """sprinkle (700 x 900, seed 6) at 24 pivots per sweep under forms 5, 6 and 7: equal pivot
+    logs, tables equal under same_bits_or_nan, form 5's equal to the oracle's."""
+    name, n, m, seed, P = "sprinkle", 700, 900, 6, 24
+    k = sv.block_k(P)
+    sv.check_pair_census(name, n, m, k, sv.pair_case_census(name, n, m, seed, P, _cus()))
+    block_mode(P)
+    _, Tref, st, done, log = sv.reference(name, n, m, seed, k)
+    out = {}
+    for form in (5, 6, 7):
+        sweep_form(form)
+        dev, ctl = _device_chain(sv.scenario(name, n, m, seed), n, m, P, sv.pair_chain(P))
+        out[form] = (int(ctl["npivots"]), dev.read_log(0, done).copy(), dev.download())
+        dev.close()
+    assert out[5][0] == done == k
+    assert np.array_equal(out[5][1], log)
+    sv.same_table_as_oracle(out[5][2], Tref, n, m, name)
+    for form in (6, 7):
+        assert out[form][0] == out[5][0], form
+        assert np.array_equal(out[form][1], out[5][1]), form
+        assert sv.same_bits_or_nan(out[form][2], out[5][2]), \
+            (form, sv.first_difference(out[form][2], out[5][2]))
+
+
+@pytest.mark.parametrize("light", [False, True])
+def test_sharded_mixed_pairs_vs_oracle(sweep_form, small_grid, light):
+    """mixed_pair_table(2000, 1023) on 2 simulated ranks in the pair layout: 1000 rows and the
+    f-row each, 7 to 8 rows per wave; 13 pivots per sweep as blocks of 13, 12 and 4.  Every rank's
+    log and the assembled table against the unsharded oracle."""
+    from oracle import c_oracle
+    from test_gpu_block_sharded import _backends, _lockstep, _result
+    n, m, P, world = 2000, 1023, 13, 2
+    k = sv.block_k(P)
+    T = mixed_pair_table(n, m)
+    Tref, st, done, log = c_oracle.run(T, n, m, m, k, threads=8)
+    assert (st, done) == (0, k)
+    sweep_form(7)
+    bes = _backends(T, n, m, world, P)
+    for c in sv.pair_chain(P):
+        _lockstep(bes, c, P, light)
+    states, logs, tables, full = _result(bes)
+    for s, lg in zip(states, logs):
+        assert s["npivots"] == done and not s["term"]
+        assert np.array_equal(lg, log)
+    for t in tables[1:]:   # every f-row replica identical
+        assert np.array_equal(t[-1, :m].view(np.int64), tables[0][-1, :m].view(np.int64))
+    assert np.array_equal(full[:n].view(np.int64), Tref[:n].view(np.int64)), \
+        sv.first_difference(full[:n], Tref[:n])
+    assert np.array_equal(full[n, :m].view(np.int64), Tref[n, :m].view(np.int64))
