@@ -355,6 +355,59 @@ int smx_batch_solution_from(const double* final, const int32_t* dims, int32_t B,
                             const int32_t* nonbasis0, int32_t group, double* x, double* duals,
                             double* objective, int32_t* basis, int32_t* nonbasis, void* stream);
 
+/* ---- new constraints: warm re-solves after rows are added (smx_cuts.hpp) ----------------------
+ * "I have a new constraint; what is the optimum now?"  T is a final table ([n+1][m+1], f-row =
+ * row n, "-b" = column m) under the labels basis[p] / nonbasis[j] as smx_batch_solution writes
+ * them.  A cut is a row g[0..m] in the format of a constraint of the ORIGINAL problem:
+ * y = sum_k g[k] * x_k + g[m] >= 0.  A cut set holds K' cuts; its extended table E has n + K'
+ * constraint rows:
+ *   rows 0..n-1 are T's bits; row n + K' is T's row n (the f-row), bit for bit;
+ *   row n + kappa, for every column j = 0..m:
+ *        v = g[nonbasis[j]]   if j < m and 0 <= nonbasis[j] < m (the cut's own bits, a -0.0 kept)
+ *        v = g[m]             if j == m
+ *        v = +0.0             otherwise
+ *        for p = 0..n-1 ascending: if basis[p] = k, 0 <= k < m, and g[k] != 0: v = v + g[k] * T[p][j]
+ *        E[n+kappa][j] = v
+ * Every product is rounded on its own, the sum runs strictly in that order, there is no FMA.  A
+ * g[k] that compares equal to zero is skipped, so it cannot turn an inf of T into NaN; a NaN g[k]
+ * is applied.  A label code outside 0..n+m-1 names nothing and is skipped.  The new rows' labels
+ * are m + n + kappa ('y{n+kappa+1}'): the code the constraint would have had if appended to the
+ * original problem, so no existing code moves; dims becomes (n + K', m, flen) and func is unchanged.
+ * Values are formed whatever the base run's status.  Cuts are independent of each other and are
+ * written in the original variables only.  Under identity labels E is the enlarged original
+ * problem bit for bit, and E is one bit pattern in any implementation.  E is an equivalent form
+ * of the enlarged LP under T's labels and a violated cut shows as a negative "-b", which is what
+ * the selection rule's first phase looks for; that rule is no dual simplex, though, and such a
+ * warm run need not terminate where a cold solve would: a caller reads its status.
+ *
+ * smx_batch_cuts (device pointers, after smx_batch_solution): final fp64 [B][Rmax][ldb], dims
+ * int32 [B][3], basis int32 [B][Rmax], nonbasis int32 [B][ldb], cuts fp64 [B][S][K][ldb] (entry
+ * m_b of a row is its constant; entries past m_b are not read), ncuts int32 [B][S]; outputs tabs_c
+ * fp64 [B*S][Rmax_out][ldb], dims_c int32 [B*S][3], basis_c int32 [B*S][Rmax_out] (the base
+ * labels, the new codes, then -1); cut set q = b * S + s belongs to LP b.  The output block is
+ * written whole: rows 0..n-1 are T's rows with their padding columns, the f-row moves to row
+ * n + K' with its padding, new rows hold +0.0 past column m and the rows past n + K' hold +0.0.
+ * A set with ncuts outside 0..K or with n_b + ncuts >= Rmax_out counts as a set of 0 cuts (a
+ * relayout of T); an LP without 1 <= n_b < Rmax and 1 <= m_b < ldb is handled as n_b = Rmax - 1
+ * with 0 cuts and keeps its dims.  Returns hipErrorInvalidValue (1) before any HIP call for
+ * B < 0, S < 0, K < 0, Rmax_out < Rmax, B * S past 2^31 - 1, (Rmax, ldb) or (Rmax_out, ldb) outside
+ * smx_batch_cuts_fits or, with B * S > 0, a null pointer (cuts may be null when K == 0); B == 0 or
+ * S == 0 returns 0 without a launch. */
+int smx_batch_cuts(const double* final, const int32_t* dims, int32_t B, int32_t S, int32_t Rmax,
+                   int32_t ldb, const int32_t* basis, const int32_t* nonbasis, const double* cuts,
+                   const int32_t* ncuts, int32_t K, int32_t Rmax_out, double* tabs_c,
+                   int32_t* dims_c, int32_t* basis_c, void* stream);
+/* Host only: 1 inside the envelope (that of smx_batch_scenario_fits, applied to the output
+ * block), else 0. */
+int smx_batch_cuts_fits(int32_t Rmax_out, int32_t ldb);
+/* The same rule on one HOST table with leading dimension ld >= m + 1 (synchronous): G [K][m+1];
+ * E_out [n+K+1][ld_out] (ld_out >= m + 1; columns 0..m of every row are written; it must not
+ * overlap T) and basis_out [n+K].  -1 for a null pointer (G may be null when K == 0), n < 1,
+ * m < 1, K < 0, ld < m + 1 or ld_out < m + 1. */
+int smx_host_cuts(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                  const int32_t* nonbasis, const double* G, int32_t K, double* E_out,
+                  int64_t ld_out, int32_t* basis_out);
+
 /* ---- row-sharded engine (one process per GPU; exchange = caller's all-gather) ----------
  * Local tableau: shape->rows constraint rows (global rows row0 .. row0+rows-1) + a replica
  * of the f-row as local row `rows`.  Per pivot:

@@ -17,6 +17,9 @@
 //                     one workgroup per LP) and host_ranging, its host twin
 //   smx_scenario.hpp  k_batch_scenario (a batch's final tables, labels and deltas -> the tables
 //                     warm re-solves start from, one workgroup per scenario) and host_scenario
+//   smx_cuts.hpp      k_batch_cuts (a batch's final tables, labels and new constraint rows -> the
+//                     extended tables warm re-solves start from, one workgroup per cut set) and
+//                     host_cuts
 //   smx_resident.hpp  k_resident: the whole pivot loop in one persistent launch, tableau in LDS
 //   smx_block.hpp     k_blk_*: P pivots per HBM sweep, decisions planned from the sweep's input
 //   smx_sweep.hpp     k_blk_sweep, k_blk_sweep_rest: the sweep itself
@@ -66,6 +69,7 @@ static_assert(sizeof(smx_part) == 32, "smx_part layout");
 #include "smx_solution.hpp"
 #include "smx_ranging.hpp"
 #include "smx_scenario.hpp"
+#include "smx_cuts.hpp"
 #include "smx_resident.hpp"
 #include "smx_block.hpp"
 #include "smx_sweep.hpp"
@@ -1377,6 +1381,40 @@ int smx_host_scenario(const double* T, int64_t ld, int32_t n, int32_t m, const i
         m < 1 || ld < (int64_t)m + 1 || ld_out < (int64_t)m + 1 || (int64_t)n + m > INT32_MAX)
         return -1;
     host_scenario(T, ld, n, m, basis, nonbasis, func, drhs, dcost, S_out, ld_out, func_out);
+    return 0;
+}
+
+// ---- new constraints: the extended tables warm re-solves start from (smx_cuts.hpp) ------------
+// The envelope is smx_batch_scenario_fits applied to the output block; the kernel holds no LDS.
+int smx_batch_cuts_fits(int32_t Rmax_out, int32_t ldb) {
+    return sol_lds_bytes(Rmax_out, ldb) >= 0;
+}
+
+int smx_batch_cuts(const double* final, const int32_t* dims, int32_t B, int32_t S_, int32_t Rmax,
+                   int32_t ldb, const int32_t* basis, const int32_t* nonbasis, const double* cuts,
+                   const int32_t* ncuts, int32_t K, int32_t Rmax_out, double* tabs_c,
+                   int32_t* dims_c, int32_t* basis_c, void* stream) {
+    if (B < 0 || S_ < 0 || K < 0 || Rmax_out < Rmax || sol_lds_bytes(Rmax, ldb) < 0 ||
+        sol_lds_bytes(Rmax_out, ldb) < 0 || (int64_t)B * S_ > INT32_MAX)
+        return (int)hipErrorInvalidValue;
+    if (B == 0 || S_ == 0) return 0;
+    if (!final || !dims || !basis || !nonbasis || (!cuts && K > 0) || !ncuts || !tabs_c ||
+        !dims_c || !basis_c)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_batch_cuts, dim3((unsigned)(B * S_)), dim3(kCutBlock), 0, S(stream),
+                       final, dims, B, S_, Rmax, ldb, basis, nonbasis, cuts, ncuts, K, Rmax_out,
+                       tabs_c, dims_c, basis_c);
+    return (int)hipGetLastError();
+}
+
+int smx_host_cuts(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                  const int32_t* nonbasis, const double* G, int32_t K, double* E_out,
+                  int64_t ld_out, int32_t* basis_out) {
+    if (!T || !basis || !nonbasis || (!G && K > 0) || !E_out || !basis_out || n < 1 || m < 1 ||
+        K < 0 || ld < (int64_t)m + 1 || ld_out < (int64_t)m + 1 ||
+        (int64_t)n + m + K > INT32_MAX)
+        return -1;
+    host_cuts(T, ld, n, m, basis, nonbasis, G, K, E_out, ld_out, basis_out);
     return 0;
 }
 

@@ -29,6 +29,12 @@ move: what is the optimum now?" without solving the perturbed problems from scra
 basis on the device, and the same solve kernel carries on from that table -- a handful of pivots
 where a cold solve takes hundreds.  Such a warm run need not terminate: every
 scenario reports its status, and the object-level call falls back to a cold solve.
+
+``solve_batch_cuts`` (and ``solve_batch_cuts_arrays``) answer "I have new constraints: what is the
+optimum now?" in the same way: ``k_batch_cuts`` (csrc/smx_cuts.hpp) writes every cut, given in the
+original variables, as one more row under its LP's final basis, and the solve kernel that takes
+the enlarged block carries on from there.  The same caveat holds and the same cold
+fallback answers it.
 """
 from __future__ import annotations
 
@@ -830,6 +836,276 @@ def solve_batch_scenarios(problems, scenarios, max_pivots: int = 256, warm_pivot
                 if sc.status not in ("optimum", "exception")]
         if todo:
             cold = [_perturbed(*problems[k], *scenarios[k][s]) for k, s in todo]
+            sols, sts = solve_batch_solutions(cold, max_pivots, device, kernel)
+            for (k, s), sol, st in zip(todo, sols, sts):
+                results[k][1][s] = Scenario(sol, st, False)
+    return results
+
+
+def cuts_fits(Rmax_out: int, ldb: int) -> bool:
+    """Whether output blocks of Rmax_out x ldb are inside k_batch_cuts's envelope (the library is
+    the one source of the rule)."""
+    if not (0 <= Rmax_out < 1 << 31 and 0 <= ldb < 1 << 31):
+        return False
+    return bool(_lib.load().smx_batch_cuts_fits(int(Rmax_out), int(ldb)))
+
+
+_TIERS = ("wave", "workgroup", "global")
+
+
+def warm_kernel(base: str, Rmax_out: int, ldb: int) -> str:
+    """The kernel the enlarged tables of a cut launch run on: the first tier at or above the base
+    run's (``"wave"`` < ``"workgroup"`` < ``"global"``) that takes Rmax_out x ldb blocks.  Raises
+    ValueError when none does."""
+    for which in _TIERS[_TIERS.index(base):]:
+        try:
+            return choose_kernel(Rmax_out, ldb, which)
+        except ValueError:
+            continue
+    raise ValueError(ENVELOPE_ERROR)
+
+
+def solve_batch_cuts_arrays(tabs: np.ndarray, dims: np.ndarray, cuts: np.ndarray,
+                            ncuts: np.ndarray, max_pivots: int = 256, warm_pivots=None,
+                            device=None, kernel: str = "auto", ranging: bool = False,
+                            log: bool = False) -> dict:
+    """Array-level solve with new constraints: every LP of ``tabs`` / ``dims`` (as in
+    ``solve_batch_arrays``) and S cut sets of each.  ``cuts``: float64 [B][S][K][ldb], row
+    ``cuts[k, s, c]`` is a constraint of problem k in the format of its own rows (entry m_k the
+    constant; entries past it are not read); ``ncuts``: int32 [B][S], how many of the K rows set
+    s of problem k holds (0..K, else ValueError).
+
+    One stream, no host round trip between the steps: the base solve, ``smx_batch_solution``
+    (``ranging``: ``smx_batch_ranging``), then ``smx_batch_cuts`` (the extended tables of Rmax + K
+    rows under every LP's final labels, include/smx.h), the warm solve of all B * S tables capped
+    at ``warm_pivots`` (default: ``max_pivots``), ``smx_batch_solution_from`` (group 1: every
+    table starts from its own extended labels) and, with ``ranging``, ``smx_batch_ranging`` on
+    the warm runs' final tables.  The warm solve's kernel is chosen again for (Rmax + K, ldb)
+    (``warm_kernel``): a launch may leave the wavefront tier for the workgroup tier or the LDS
+    edge for the global-memory tier; a shape that leaves every tier raises ValueError.  The
+    extended tables are made in slices of S that keep them under ``GM_TABLE_BUDGET``.
+
+    Returns ``base`` exactly as ``solve_batch_scenarios_arrays`` does; and per cut set, shaped
+    [B][S]...: ``status``, ``npivots`` (the warm pivots only; with ``log`` also their log ``rc``
+    [warm_pivots][2], B * S * warm_pivots * 8 bytes to copy back), ``x`` [ldb - 1], ``duals``
+    [Rmax + K - 1] (the new constraints' included, at n_k..n_k + ncuts - 1), ``objective``,
+    ``basis`` [Rmax + K - 1], ``nonbasis`` [ldb - 1] and with ``ranging`` the four range arrays.
+    A new constraint's label code is m_k + n_k + c.  A warm run need not terminate where a cold
+    solve of the enlarged problem would (the selection rule is no dual simplex): read ``status``;
+    SMX_PIVOT there means ``warm_pivots`` was reached."""
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    tabs = np.ascontiguousarray(tabs, dtype=np.float64)
+    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    cuts = np.ascontiguousarray(cuts, dtype=np.float64)
+    ncuts = np.ascontiguousarray(ncuts, dtype=np.int32)
+    B, Rmax, ldb = tabs.shape
+    if dims.shape != (B, 3):
+        raise ValueError("dims must be int32 [B][3]")
+    if cuts.ndim != 4 or cuts.shape[0] != B or cuts.shape[3] != ldb:
+        raise ValueError("cuts must be float64 [B][S][K][ldb]")
+    S, K = cuts.shape[1], cuts.shape[2]
+    if ncuts.shape != (B, S):
+        raise ValueError("ncuts must be int32 [B][S]")
+    if ((ncuts < 0) | (ncuts > K)).any():
+        raise ValueError("ncuts must lie in 0..K")
+    if not torch.cuda.is_available():
+        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
+    Rout = Rmax + K
+    which = choose_kernel(Rmax, ldb, kernel) if B else "wave"
+    warm = warm_kernel(which, Rout, ldb) if B else "wave"
+    if B and ((dims[:, 0] + 1 > Rmax).any() or (dims[:, 1] + 1 > ldb).any() or
+              (dims[:, 1] < 1).any() or (dims[:, 0] < 1).any()):
+        raise ValueError(ENVELOPE_ERROR)
+    if solution_lds_bytes(Rout, ldb) < 0 or not cuts_fits(Rout, ldb):
+        raise ValueError(ENVELOPE_ERROR)
+    if ranging and not ranging_fits(Rout, ldb):
+        raise ValueError(ENVELOPE_ERROR)
+    P = int(max_pivots)
+    Pw = P if warm_pivots is None else int(warm_pivots)
+    L = _lib.load()
+    solvers = {"wave": (L.smx_batch_solve, "smx_batch_solve"),
+               "workgroup": (L.smx_batch_solve_wg, "smx_batch_solve_wg"),
+               "global": (L.smx_batch_solve_gm, "smx_batch_solve_gm")}
+    per = max(1, min(S, GM_TABLE_BUDGET // max(1, B * Rout * ldb * 8)))
+    dev = torch.device(device if device is not None else "cuda")
+
+    def run(tier, d_in, d_dims_, count, rows, cap):
+        solve, what = solvers[tier]
+        d_out = torch.empty_like(d_in)
+        d_rc = torch.zeros((count, max(cap, 1), 2), dtype=torch.int32, device=dev)
+        d_xv = torch.zeros((count, max(cap, 1), 2), dtype=torch.float64, device=dev)
+        d_st = torch.zeros(count, dtype=torch.int32, device=dev)
+        d_np = torch.zeros(count, dtype=torch.int32, device=dev)
+        _lib.check(solve(d_in.data_ptr(), d_dims_.data_ptr(), count, rows, ldb, cap,
+                         d_out.data_ptr(), d_rc.data_ptr(), d_xv.data_ptr(), None,
+                         d_st.data_ptr(), d_np.data_ptr(), stream.cuda_stream), what)
+        return d_out, d_rc, d_xv, d_st, d_np
+
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        d_tabs = torch.from_numpy(tabs).to(dev)
+        d_dims = torch.from_numpy(dims).to(dev)
+        d_cuts = torch.from_numpy(cuts).to(dev)
+        d_nc = torch.from_numpy(ncuts).to(dev)
+        d_out, d_rc, d_xv, d_st, d_np = run(which, d_tabs, d_dims, B, Rmax, P)
+        d_func = d_tabs[torch.arange(B, device=dev), d_dims[:, 0].long()].contiguous()
+        sol = _device_solution(L, stream, dev, d_out, d_dims, B, Rmax, ldb, P, d_rc, d_np, d_func)
+        rng = (_device_ranging(L, stream, dev, d_out, d_dims, B, Rmax, ldb, sol[3], sol[4])
+               if ranging else None)
+        slices = []
+        for s0 in range(0, S, per):
+            c = min(S, s0 + per) - s0
+            Q = B * c
+            d_tc = torch.empty((Q, Rout, ldb), dtype=torch.float64, device=dev)
+            d_dc = torch.empty((Q, 3), dtype=torch.int32, device=dev)
+            d_bc = torch.empty((Q, Rout), dtype=torch.int32, device=dev)
+            d_cs = d_cuts[:, s0:s0 + c].contiguous()         # named: alive until the launch
+            d_ns = d_nc[:, s0:s0 + c].contiguous()
+            _lib.check(L.smx_batch_cuts(
+                d_out.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, sol[3].data_ptr(),
+                sol[4].data_ptr(), d_cs.data_ptr() if K else None, d_ns.data_ptr(), K, Rout,
+                d_tc.data_ptr(), d_dc.data_ptr(), d_bc.data_ptr(), stream.cuda_stream),
+                "smx_batch_cuts")
+            d_wout, d_wrc, _, d_wst, d_wnp = run(warm, d_tc, d_dc, Q, Rout, Pw)
+            # every table's own start labels (group 1): its LP's column labels and function row
+            d_n0 = sol[4].repeat_interleave(c, dim=0)
+            d_fq = d_func.repeat_interleave(c, dim=0)
+            wsol = _device_solution(L, stream, dev, d_wout, d_dc, Q, Rout, ldb, Pw, d_wrc, d_wnp,
+                                    d_fq, start=(d_bc, d_n0, 1))
+            wrng = (_device_ranging(L, stream, dev, d_wout, d_dc, Q, Rout, ldb, wsol[3], wsol[4])
+                    if ranging else None)
+            slices.append((c, d_wst, d_wnp, d_wrc, wsol, wrng))
+            del d_tc, d_wout
+        # everything is enqueued: only now does anything come back
+        base = {"rc": d_rc.cpu().numpy(), "xv": d_xv.cpu().numpy(),
+                "status": d_st.cpu().numpy(), "npivots": d_np.cpu().numpy()}
+        base.update(_solution_arrays(sol, Rmax, ldb, (B,)))
+        if ranging:
+            base.update(_ranging_arrays(rng, Rmax, ldb, (B,)))
+        parts = []
+        for c, d_wst, d_wnp, d_wrc, wsol, wrng in slices:
+            part = {"status": d_wst.cpu().numpy().reshape(B, c),
+                    "npivots": d_wnp.cpu().numpy().reshape(B, c)}
+            if log:
+                part["rc"] = d_wrc.cpu().numpy().reshape(B, c, max(Pw, 1), 2)
+            part.update(_solution_arrays(wsol, Rout, ldb, (B, c)))
+            if ranging:
+                part.update(_ranging_arrays(wrng, Rout, ldb, (B, c)))
+            parts.append(part)
+    res = {"base": base}
+    if parts:
+        for key in parts[0]:
+            res[key] = np.concatenate([p[key] for p in parts], axis=1)
+    else:                                                    # S == 0
+        res.update({"status": np.zeros((B, 0), np.int32), "npivots": np.zeros((B, 0), np.int32),
+                    "x": np.zeros((B, 0, ldb - 1)), "duals": np.zeros((B, 0, Rout - 1)),
+                    "objective": np.zeros((B, 0)),
+                    "basis": np.zeros((B, 0, Rout - 1), np.int32),
+                    "nonbasis": np.zeros((B, 0, ldb - 1), np.int32)})
+        if log:
+            res["rc"] = np.zeros((B, 0, max(Pw, 1), 2), np.int32)
+        if ranging:
+            res.update({"rhs_lo": np.zeros((B, 0, Rout - 1)), "rhs_hi": np.zeros((B, 0, Rout - 1)),
+                        "cost_lo": np.zeros((B, 0, ldb - 1)), "cost_hi": np.zeros((B, 0, ldb - 1))})
+    return res
+
+
+def _enlarged(cons, func, rows):
+    """The ORIGINAL problem with a cut set's rows appended."""
+    return [list(r) for r in cons] + [[float(v) for v in r] for r in rows], list(func)
+
+
+def _fallback_cuts(cons, func, sets, max_pivots, warm_pivots):
+    try:
+        sm = SimplexMethod(cons, func)
+        sm.solve(record_history=False, max_pivots=max_pivots)
+        base = sm.solution()
+        out = []
+        for rows in sets:
+            ext = sm.add_constraints(rows)
+            ext.solve(record_history=False, max_pivots=warm_pivots)
+            out.append(Scenario(ext.solution(), ext.status, True))
+        return base, out
+    except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
+        return exc, [Scenario(exc, "exception", True) for _ in sets]
+
+
+def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
+                     cold_fallback: bool = True, device=None, kernel: str = "auto"):
+    """Solve every ``(constraints, function)`` and, for each of its cut sets, the problem with
+    that set's constraints added; ``cuts[k]`` is a list of cut sets of problem k, each a list of
+    rows in the constraints' own format ([m coefficients, constant]; an empty set adds nothing).
+    Returns per problem ``(Solution, [Scenario])``: the base answer as ``solve_batch_solutions``
+    gives it and one ``Scenario`` per cut set, in order, whose ``Solution`` has n + K' duals and
+    row labels (a new constraint's code is m + n + c).
+
+    Routing and launch grouping are ``solve_batch_solutions``'s; inside a launch the set counts
+    and sizes are padded with empty sets and dropped again (``solve_batch_cuts_arrays``).
+    Problems routed ``"single"``, and those of a launch whose enlarged tables leave every batch
+    kernel's envelope, go through ``SimplexMethod.add_constraints``.  A warm run is capped at
+    ``warm_pivots`` (default ``max_pivots``) and need not terminate; with ``cold_fallback``
+    every set whose warm run did not end at ``"optimum"`` is solved cold from the enlarged
+    original through ``solve_batch_solutions`` with the full ``max_pivots`` and marked
+    ``warm=False``."""
+    problems = list(problems)
+    cuts = [[[list(r) for r in rows] for rows in sets] for sets in cuts]
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    if len(cuts) != len(problems):
+        raise ValueError("cuts must hold one list of cut sets per problem")
+    for (c, _), sets in zip(problems, cuts):
+        if any(len(r) != len(c[0]) for rows in sets for r in rows):
+            raise ValueError("a cut must have the length of its problem's constraints")
+    if not torch.cuda.is_available():
+        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
+    P = int(max_pivots)
+    Pw = P if warm_pivots is None else int(warm_pivots)
+    results = [None] * len(problems)
+    routes = _routes(problems, kernel)
+    for k, (c, f) in enumerate(problems):
+        if routes[k] == "single":
+            results[k] = _fallback_cuts(c, f, cuts[k], P, Pw)
+    for which, idx in _launches(problems, routes, max_pivots, False):
+        tabs, dims = pack([problems[k] for k in idx])
+        _, Rmax, ldb = tabs.shape
+        S = max(len(cuts[k]) for k in idx)
+        K = max((len(rows) for k in idx for rows in cuts[k]), default=0)
+        try:
+            warm_kernel(which, Rmax + K, ldb)
+        except ValueError:
+            for k in idx:
+                results[k] = _fallback_cuts(*problems[k], cuts[k], P, Pw)
+            continue
+        g = np.zeros((len(idx), S, K, ldb), dtype=np.float64)
+        nc = np.zeros((len(idx), S), dtype=np.int32)
+        for q, k in enumerate(idx):
+            m = int(dims[q, 1])
+            for s, rows in enumerate(cuts[k]):
+                nc[q, s] = len(rows)
+                if rows:
+                    g[q, s, :len(rows), :m + 1] = np.asarray(rows, dtype=np.float64)
+        out = solve_batch_cuts_arrays(tabs, dims, g, nc, P, Pw, device, kernel=which)
+        base = out["base"]
+        for q, k in enumerate(idx):
+            n, m = int(dims[q, 0]), int(dims[q, 1])
+            sol = Solution(base["x"][q, :m].copy(), base["duals"][q, :n].copy(),
+                           float(base["objective"][q]), base["basis"][q, :n].copy(),
+                           base["nonbasis"][q, :m].copy(), int(base["npivots"][q]))
+            answers = []
+            for s, rows in enumerate(cuts[k]):
+                np_, n2 = int(out["npivots"][q, s]), n + len(rows)
+                answers.append(Scenario(
+                    Solution(out["x"][q, s, :m].copy(), out["duals"][q, s, :n2].copy(),
+                             float(out["objective"][q, s]), out["basis"][q, s, :n2].copy(),
+                             out["nonbasis"][q, s, :m].copy(), np_),
+                    _status_name(int(out["status"][q, s]), np_, Pw), True))
+            results[k] = (sol, answers)
+    if cold_fallback:
+        todo = [(k, s) for k, (_, answers) in enumerate(results) for s, sc in enumerate(answers)
+                if sc.status not in ("optimum", "exception")]
+        if todo:
+            cold = [_enlarged(*problems[k], cuts[k][s]) for k, s in todo]
             sols, sts = solve_batch_solutions(cold, max_pivots, device, kernel)
             for (k, s), sol, st in zip(todo, sols, sts):
                 results[k][1][s] = Scenario(sol, st, False)

@@ -550,6 +550,65 @@ class SimplexMethod:
         new._tracker = None
         return new
 
+    def add_constraints(self, rows) -> "SimplexMethod":
+        """A new ``SimplexMethod`` on the extended table of the current one: every row of
+        ``rows`` ([m coefficients, constant], the format of a constraint of the ORIGINAL problem)
+        becomes one more constraint row under the labels this table stands under, the f-row moves
+        below them.  The labels come from ``row`` / ``column``, the table from the backend's
+        ``download()`` (the caller's own lists before the first pivot), the rule from
+        ``smx_host_cuts`` (include/smx.h) -- on every backend, so this is correct everywhere and
+        fast nowhere special.  The result lives on the same backend: ``column`` is extended by
+        'y{n+1}'.., ``row`` and ``function`` are unchanged, its pivot log starts empty, and
+        ``solve()``, ``solution()`` and ``ranging()`` carry on from there.  Such a warm run need
+        not terminate (the selection rule is no dual simplex): cap it with ``max_pivots`` and
+        read ``status``."""
+        n, m = self.n, self.m
+        rows = [list(r) for r in rows]
+        if any(len(r) != m + 1 for r in rows):
+            raise ValueError(f"a new constraint must hold {m} coefficients and a constant")
+        K = len(rows)
+        G = np.ascontiguousarray(rows, dtype=np.float64).reshape(K, m + 1)
+        basis = np.array([_label_code(s, m) for s in self.column[:n]], dtype=np.int32)
+        nonbasis = np.array([_label_code(s, m) for s in self.row[:m]], dtype=np.int32)
+        if self._pristine:        # the caller's own lists; a short f-row reads as +0.0
+            T = np.zeros((n + 1, m + 1), dtype=np.float64)
+            T[:n] = self._initial[:n]
+            frow = self._initial[n][:m + 1]
+            T[n, :len(frow)] = frow
+        else:
+            T = np.ascontiguousarray(self._dev.download()[:n + 1, :m + 1], dtype=np.float64)
+        E = np.empty((n + K + 1, m + 1), dtype=np.float64)
+        basis_out = np.empty(n + K, dtype=np.int32)
+        err = _lib.load().smx_host_cuts(
+            T.ctypes.data, T.shape[1], n, m, basis.ctypes.data, nonbasis.ctypes.data,
+            G.ctypes.data if K else None, K, E.ctypes.data, E.shape[1], basis_out.ctypes.data)
+        if err:
+            raise RuntimeError(f"smx_host_cuts refused n={n}, m={m}, K={K} ({err})")
+        cls = type(self)
+        new = cls.__new__(cls)
+        new.n, new.m, new.flen = n + K, m, self.flen
+        new.invalid_index = 1 + max(n + K, m)
+        new.function = list(self.function)
+        new.row = list(self.row)
+        new.column = (list(self.column[:n]) + ['y' + str(n + c + 1) for c in range(K)]
+                      + list(self.column[n:]))
+        new._initial = None
+        old = self._dev
+        if self.backend == "host":
+            new._dev = type(old)(E, n + K, m, self.flen)
+        elif self.backend == "sharded":
+            new._dev = type(old)(E, n + K, m, self.flen, old.devices, pivots=old.P,
+                                 exchange=old.exchange)
+        else:
+            new._dev = type(old)(E, n + K, m, self.flen, device=old.device)
+        new._pristine = False
+        new._int0 = new._int_hist = None
+        new.pivot_log = []
+        new.status = "ready"
+        new.cycle = None
+        new._tracker = None
+        return new
+
     # ---------------------------------------------------------------- the hot path -------
     def pick_element(self) -> (bool, int, int, float):
         """simplex.py:70-141: selection kernels on the device, outcome mapped to the
