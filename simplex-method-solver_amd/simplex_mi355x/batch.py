@@ -35,6 +35,15 @@ optimum now?" in the same way: ``k_batch_cuts`` (csrc/smx_cuts.hpp) writes every
 original variables, as one more row under its LP's final basis, and the solve kernel that takes
 the enlarged block carries on from there.  The same caveat holds and the same cold
 fallback answers it.
+
+The host side of all this is stated once.  Array level: ``_launch_arrays`` and
+``_launch_tier`` check a launch, ``_device_solve`` / ``_device_solution`` / ``_device_ranging``
+enqueue one kernel each on fresh outputs, ``_enqueue_base`` and ``_base_arrays`` are
+``solve_batch_arrays`` (and so the ``base`` of the warm calls), and ``_warm_chain`` is everything
+the two warm calls share: a warm feature hands it the callable that enqueues its table-making
+kernel.  Object level: ``_drive`` routes, falls back and launches for all five ``solve_batch*``
+calls, ``_solution_at`` builds a ``Solution``, ``_status_name`` names a status, ``_warm_answers``
+and ``_cold_tail`` serve scenarios and cuts alike.
 """
 from __future__ import annotations
 
@@ -68,44 +77,44 @@ GM_TABLE_BUDGET = 1 << 30
 GM_MIN_BATCH = 1
 
 
+def _envelope(query: str, Rmax: int, ldb: int, outside):
+    """What the library's envelope query ``query`` says of Rmax x ldb blocks; ``outside`` where
+    either is no int32, the C argument type.  The library is the one source of every rule."""
+    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
+        return outside
+    return getattr(_lib.load(), query)(int(Rmax), int(ldb))
+
+
 def wg_lds_bytes(Rmax: int, ldb: int) -> int:
     """Dynamic LDS one workgroup of k_batch_wg needs for a launch of Rmax x ldb blocks, -1 when
-    the shape is outside that kernel's envelope (the library is the one source of the rule)."""
-    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
-        return -1
-    return int(_lib.load().smx_batch_wg_lds_bytes(int(Rmax), int(ldb)))
+    the shape is outside that kernel's envelope."""
+    return int(_envelope("smx_batch_wg_lds_bytes", Rmax, ldb, -1))
 
 
 def gm_fits(Rmax: int, ldb: int) -> bool:
-    """Whether a launch of Rmax x ldb blocks is inside k_batch_gm's envelope (the library is the
-    one source of the rule)."""
-    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
-        return False
-    return bool(_lib.load().smx_batch_gm_fits(int(Rmax), int(ldb)))
+    """Whether a launch of Rmax x ldb blocks is inside k_batch_gm's envelope."""
+    return bool(_envelope("smx_batch_gm_fits", Rmax, ldb, False))
 
 
 def solution_lds_bytes(Rmax: int, ldb: int) -> int:
     """Dynamic LDS one block of k_batch_solution needs for a launch of Rmax x ldb blocks, -1 when
-    the shape is outside that kernel's envelope (the library is the one source of the rule)."""
-    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
-        return -1
-    return int(_lib.load().smx_batch_solution_lds_bytes(int(Rmax), int(ldb)))
+    the shape is outside that kernel's envelope."""
+    return int(_envelope("smx_batch_solution_lds_bytes", Rmax, ldb, -1))
 
 
 def ranging_fits(Rmax: int, ldb: int) -> bool:
-    """Whether a launch of Rmax x ldb blocks is inside k_batch_ranging's envelope (the library is
-    the one source of the rule)."""
-    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
-        return False
-    return bool(_lib.load().smx_batch_ranging_fits(int(Rmax), int(ldb)))
+    """Whether a launch of Rmax x ldb blocks is inside k_batch_ranging's envelope."""
+    return bool(_envelope("smx_batch_ranging_fits", Rmax, ldb, False))
 
 
 def scenario_fits(Rmax: int, ldb: int) -> bool:
-    """Whether a launch of Rmax x ldb blocks is inside k_batch_scenario's envelope (the library
-    is the one source of the rule)."""
-    if not (0 <= Rmax < 1 << 31 and 0 <= ldb < 1 << 31):
-        return False
-    return bool(_lib.load().smx_batch_scenario_fits(int(Rmax), int(ldb)))
+    """Whether a launch of Rmax x ldb blocks is inside k_batch_scenario's envelope."""
+    return bool(_envelope("smx_batch_scenario_fits", Rmax, ldb, False))
+
+
+def cuts_fits(Rmax_out: int, ldb: int) -> bool:
+    """Whether output blocks of Rmax_out x ldb are inside k_batch_cuts's envelope."""
+    return bool(_envelope("smx_batch_cuts_fits", Rmax_out, ldb, False))
 
 
 def _shape(cons, func):
@@ -158,8 +167,7 @@ def choose_kernel(Rmax: int, ldb: int, kernel: str = "auto") -> str:
     force one.  ``"auto"`` never answers ``"global"``: past the LDS edge it refuses, and the
     global-memory kernel is reached only by name.
     Raises ValueError when the shape fits none of the kernels allowed."""
-    if kernel not in KERNELS:
-        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    _kernel_name(kernel)
     if kernel == "global":
         if gm_fits(Rmax, ldb):
             return "global"
@@ -192,14 +200,151 @@ def _labels(n, m):
     return row, col
 
 
-def _fallback(cons, func, max_pivots, history):
-    try:
-        sm = SimplexMethod(cons, func)
-        if history:
-            return sm.get_solution(max_pivots=max_pivots), sm.status
-        return sm.solve(record_history=False, max_pivots=max_pivots), sm.status
-    except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
-        return exc, "exception"
+def _kernel_name(kernel):
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+
+
+def _need_device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
+
+
+def _launch_arrays(tabs, dims):
+    """The first half of the launch check every array-level call makes: ``tabs`` and ``dims`` as
+    contiguous float64 / int32 arrays and (B, Rmax, ldb).  Refuses a ``dims`` of another shape."""
+    tabs = np.ascontiguousarray(tabs, dtype=np.float64)
+    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    B, Rmax, ldb = tabs.shape
+    if dims.shape != (B, 3):
+        raise ValueError("dims must be int32 [B][3]")
+    return tabs, dims, (B, Rmax, ldb)
+
+
+def _launch_tier(dims, shape, kernel):
+    """The second half (the calls differ in what they refuse between the two): the tier
+    ``kernel`` puts a launch of this shape on (``choose_kernel``).  Refuses a problem of ``dims``
+    that lies outside the launch's Rmax x ldb blocks."""
+    B, Rmax, ldb = shape
+    which = choose_kernel(Rmax, ldb, kernel) if B else "wave"
+    if B and ((dims[:, 0] + 1 > Rmax).any() or (dims[:, 1] + 1 > ldb).any() or
+              (dims[:, 1] < 1).any() or (dims[:, 0] < 1).any()):
+        raise ValueError(ENVELOPE_ERROR)
+    return which
+
+
+# the library's solve entry point of every tier
+_SOLVERS = {"wave": "smx_batch_solve", "workgroup": "smx_batch_solve_wg",
+            "global": "smx_batch_solve_gm"}
+
+
+def _device_solve(L, stream, tier, d_tabs, d_dims, cap, history=False):
+    """Enqueue the solve kernel of ``tier`` on fresh outputs, capped at ``cap`` pivots; returns
+    the device tensors (final, rc, xv, status, npivots, snaps), ``snaps`` None without
+    ``history``."""
+    count, rows, ldb = d_tabs.shape
+    dev = d_tabs.device
+    d_out = torch.empty_like(d_tabs)
+    d_rc = torch.zeros((count, max(cap, 1), 2), dtype=torch.int32, device=dev)
+    d_xv = torch.zeros((count, max(cap, 1), 2), dtype=torch.float64, device=dev)
+    d_snaps = (torch.empty((count, max(cap, 1), rows, ldb), dtype=torch.float64, device=dev)
+               if history else None)
+    d_st = torch.zeros(count, dtype=torch.int32, device=dev)
+    d_np = torch.zeros(count, dtype=torch.int32, device=dev)
+    what = _SOLVERS[tier]
+    _lib.check(getattr(L, what)(
+        d_tabs.data_ptr(), d_dims.data_ptr(), count, rows, ldb, cap, d_out.data_ptr(),
+        d_rc.data_ptr(), d_xv.data_ptr(), d_snaps.data_ptr() if history else None,
+        d_st.data_ptr(), d_np.data_ptr(), stream.cuda_stream), what)
+    return d_out, d_rc, d_xv, d_st, d_np, d_snaps
+
+
+def _device_solution(L, stream, d_final, d_dims, P, d_rc, d_np, d_func, start=None):
+    """Enqueue smx_batch_solution (``start`` = (basis0, nonbasis0, group): smx_batch_solution_from)
+    on fresh outputs; returns the device tensors (x, duals, objective, basis, nonbasis)."""
+    B, Rmax, ldb = d_final.shape
+    dev = d_final.device
+    d_x = torch.empty((B, ldb), dtype=torch.float64, device=dev)
+    d_du = torch.empty((B, Rmax), dtype=torch.float64, device=dev)
+    d_obj = torch.empty(B, dtype=torch.float64, device=dev)
+    d_ba = torch.empty((B, Rmax), dtype=torch.int32, device=dev)
+    d_nb = torch.empty((B, ldb), dtype=torch.int32, device=dev)
+    head = (d_final.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, P, d_rc.data_ptr(),
+            d_np.data_ptr(), d_func.data_ptr())
+    tail = (d_x.data_ptr(), d_du.data_ptr(), d_obj.data_ptr(), d_ba.data_ptr(), d_nb.data_ptr(),
+            stream.cuda_stream)
+    if start is None:
+        _lib.check(L.smx_batch_solution(*head, *tail), "smx_batch_solution")
+    else:
+        _lib.check(L.smx_batch_solution_from(*head, start[0].data_ptr(), start[1].data_ptr(),
+                                             int(start[2]), *tail), "smx_batch_solution_from")
+    return d_x, d_du, d_obj, d_ba, d_nb
+
+
+def _device_ranging(L, stream, d_final, d_dims, d_ba, d_nb):
+    """Enqueue smx_batch_ranging on fresh outputs; returns (rhs_lo, rhs_hi, cost_lo, cost_hi)."""
+    B, Rmax, ldb = d_final.shape
+    dev = d_final.device
+    d_rl, d_rh = (torch.empty((B, Rmax), dtype=torch.float64, device=dev) for _ in "lh")
+    d_cl, d_ch = (torch.empty((B, ldb), dtype=torch.float64, device=dev) for _ in "lh")
+    _lib.check(L.smx_batch_ranging(
+        d_final.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, d_ba.data_ptr(), d_nb.data_ptr(),
+        d_rl.data_ptr(), d_rh.data_ptr(), d_cl.data_ptr(), d_ch.data_ptr(), stream.cuda_stream),
+        "smx_batch_ranging")
+    return d_rl, d_rh, d_cl, d_ch
+
+
+def _cut(d, lead):
+    """[count][width] on the device -> ``lead`` + [width - 1] on the host: the kernels write rows
+    of Rmax / ldb entries whose last stands for the f-row / the '-b' column and holds nothing."""
+    return d[:, :d.shape[1] - 1].contiguous().cpu().numpy().reshape(*lead, d.shape[1] - 1)
+
+
+def _solution_arrays(sol, lead):
+    """The host arrays of a ``_device_solution`` result, reshaped to ``lead`` + [...]."""
+    d_x, d_du, d_obj, d_ba, d_nb = sol
+    return {"x": _cut(d_x, lead), "duals": _cut(d_du, lead),
+            "objective": d_obj.cpu().numpy().reshape(*lead),
+            "basis": _cut(d_ba, lead), "nonbasis": _cut(d_nb, lead)}
+
+
+def _ranging_arrays(rng, lead):
+    return dict(zip(("rhs_lo", "rhs_hi", "cost_lo", "cost_hi"), (_cut(d, lead) for d in rng)))
+
+
+def _enqueue_base(L, stream, tier, d_tabs, d_dims, P, history=False, solution=True,
+                  ranging=False):
+    """Enqueue a launch's solve on ``tier`` and, as asked, its solution and its ranges; returns
+    (the ``_device_solve`` tensors, the original objective rows, the ``_device_solution`` tensors,
+    the ``_device_ranging`` tensors), None for what was not asked.  Nothing comes back yet:
+    ``_base_arrays`` does that."""
+    run = _device_solve(L, stream, tier, d_tabs, d_dims, P, history)
+    d_func = sol = rng = None
+    if solution:
+        # the original objective rows (row n_k of problem k), gathered on the device
+        d_func = d_tabs[torch.arange(len(d_tabs), device=d_tabs.device),
+                        d_dims[:, 0].long()].contiguous()
+        sol = _device_solution(L, stream, run[0], d_dims, P, run[1], run[4], d_func)
+    if ranging:
+        rng = _device_ranging(L, stream, run[0], d_dims, sol[3], sol[4])
+    return run, d_func, sol, rng
+
+
+def _base_arrays(run, sol, rng, tables=False):
+    """The result dict of ``solve_batch_arrays`` from what ``_enqueue_base`` enqueued."""
+    d_out, d_rc, d_xv, d_st, d_np, d_snaps = run
+    res = {"final": d_out.cpu().numpy()} if tables else {}
+    res.update({"rc": d_rc.cpu().numpy(), "xv": d_xv.cpu().numpy(),
+                "status": d_st.cpu().numpy(), "npivots": d_np.cpu().numpy()})
+    if sol is not None:
+        res.update(_solution_arrays(sol, (len(d_out),)))
+    if rng is not None:
+        res.update(_ranging_arrays(rng, (len(d_out),)))
+    if d_snaps is not None:
+        steps = torch.arange(d_snaps.shape[1], device=d_np.device)[None, :] < d_np[:, None]
+        res["snaps"] = d_snaps[steps].cpu().numpy()
+        res["snap_off"] = np.concatenate([[0], np.cumsum(res["npivots"], dtype=np.int64)])
+    return res
 
 
 def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256,
@@ -240,79 +385,21 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
         raise ValueError("ranging=True needs solution=True: the ranges are read off its labels")
     if not tables and history:
         raise ValueError("history=True needs the tables: tables=False cannot go with it")
-    if not torch.cuda.is_available():
-        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
-    tabs = np.ascontiguousarray(tabs, dtype=np.float64)
-    dims = np.ascontiguousarray(dims, dtype=np.int32)
-    B, Rmax, ldb = tabs.shape
-    if dims.shape != (B, 3):
-        raise ValueError("dims must be int32 [B][3]")
-    which = choose_kernel(Rmax, ldb, kernel) if B else "wave"
-    if B and ((dims[:, 0] + 1 > Rmax).any() or (dims[:, 1] + 1 > ldb).any() or
-              (dims[:, 1] < 1).any() or (dims[:, 0] < 1).any()):
+    _need_device()
+    tabs, dims, shape = _launch_arrays(tabs, dims)
+    which = _launch_tier(dims, shape, kernel)
+    if solution and solution_lds_bytes(*shape[1:]) < 0:
         raise ValueError(ENVELOPE_ERROR)
-    if solution and solution_lds_bytes(Rmax, ldb) < 0:
+    if ranging and not ranging_fits(*shape[1:]):
         raise ValueError(ENVELOPE_ERROR)
-    if ranging and not ranging_fits(Rmax, ldb):
-        raise ValueError(ENVELOPE_ERROR)
-    P = int(max_pivots)
-    L = _lib.load()
-    solve, what = {"wave": (L.smx_batch_solve, "smx_batch_solve"),
-                   "workgroup": (L.smx_batch_solve_wg, "smx_batch_solve_wg"),
-                   "global": (L.smx_batch_solve_gm, "smx_batch_solve_gm")}[which]
     dev = torch.device(device if device is not None else "cuda")
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
         d_tabs = torch.from_numpy(tabs).to(dev)
         d_dims = torch.from_numpy(dims).to(dev)
-        d_out = torch.empty_like(d_tabs)
-        d_rc = torch.zeros((B, max(P, 1), 2), dtype=torch.int32, device=dev)
-        d_xv = torch.zeros((B, max(P, 1), 2), dtype=torch.float64, device=dev)
-        d_snaps = (torch.empty((B, max(P, 1), Rmax, ldb), dtype=torch.float64, device=dev)
-                   if history else None)
-        d_st = torch.zeros(B, dtype=torch.int32, device=dev)
-        d_np = torch.zeros(B, dtype=torch.int32, device=dev)
-        _lib.check(solve(
-            d_tabs.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, P, d_out.data_ptr(),
-            d_rc.data_ptr(), d_xv.data_ptr(), d_snaps.data_ptr() if history else None,
-            d_st.data_ptr(), d_np.data_ptr(), stream.cuda_stream), what)
-        res = {"final": d_out.cpu().numpy()} if tables else {}
-        res.update({"rc": d_rc.cpu().numpy(), "xv": d_xv.cpu().numpy(),
-                    "status": d_st.cpu().numpy(), "npivots": d_np.cpu().numpy()})
-        if solution:
-            # the original objective rows (row n_k of problem k), gathered on the device
-            d_func = d_tabs[torch.arange(B, device=dev), d_dims[:, 0].long()].contiguous()
-            d_x = torch.empty((B, ldb), dtype=torch.float64, device=dev)
-            d_du = torch.empty((B, Rmax), dtype=torch.float64, device=dev)
-            d_obj = torch.empty(B, dtype=torch.float64, device=dev)
-            d_ba = torch.empty((B, Rmax), dtype=torch.int32, device=dev)
-            d_nb = torch.empty((B, ldb), dtype=torch.int32, device=dev)
-            _lib.check(L.smx_batch_solution(
-                d_out.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, P, d_rc.data_ptr(),
-                d_np.data_ptr(), d_func.data_ptr(), d_x.data_ptr(), d_du.data_ptr(),
-                d_obj.data_ptr(), d_ba.data_ptr(), d_nb.data_ptr(), stream.cuda_stream),
-                "smx_batch_solution")
-            res.update({"x": d_x[:, :ldb - 1].contiguous().cpu().numpy(),
-                        "duals": d_du[:, :Rmax - 1].contiguous().cpu().numpy(),
-                        "objective": d_obj.cpu().numpy(),
-                        "basis": d_ba[:, :Rmax - 1].contiguous().cpu().numpy(),
-                        "nonbasis": d_nb[:, :ldb - 1].contiguous().cpu().numpy()})
-        if ranging:
-            d_rl, d_rh = (torch.empty((B, Rmax), dtype=torch.float64, device=dev) for _ in "lh")
-            d_cl, d_ch = (torch.empty((B, ldb), dtype=torch.float64, device=dev) for _ in "lh")
-            _lib.check(L.smx_batch_ranging(
-                d_out.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, d_ba.data_ptr(),
-                d_nb.data_ptr(), d_rl.data_ptr(), d_rh.data_ptr(), d_cl.data_ptr(),
-                d_ch.data_ptr(), stream.cuda_stream), "smx_batch_ranging")
-            res.update({"rhs_lo": d_rl[:, :Rmax - 1].contiguous().cpu().numpy(),
-                        "rhs_hi": d_rh[:, :Rmax - 1].contiguous().cpu().numpy(),
-                        "cost_lo": d_cl[:, :ldb - 1].contiguous().cpu().numpy(),
-                        "cost_hi": d_ch[:, :ldb - 1].contiguous().cpu().numpy()})
-        if history:
-            steps = torch.arange(max(P, 1), device=dev)[None, :] < d_np[:, None]
-            res["snaps"] = d_snaps[steps].cpu().numpy()
-            res["snap_off"] = np.concatenate([[0], np.cumsum(res["npivots"], dtype=np.int64)])
-    return res
+        run, _, sol, rng = _enqueue_base(_lib.load(), torch.cuda.current_stream(dev), which,
+                                         d_tabs, d_dims, int(max_pivots), history, solution,
+                                         ranging)
+        return _base_arrays(run, sol, rng, tables)
 
 
 def pack(problems):
@@ -412,6 +499,62 @@ def _launches(problems, routes, max_pivots, history):
     return launches
 
 
+def _status_name(status, np_, P):
+    if status == _lib.OPTIMUM:
+        return "optimum"
+    if status in MESSAGES:
+        return "error"
+    if status == _lib.PIVOT and np_ >= P:
+        return "cap"
+    raise RuntimeError(f"unexpected batch status {status}")
+
+
+def _solution_at(arrays, index, n, m):
+    """The ``Solution`` of the LP at ``index`` (q, or (q, s) of a warm result) of the arrays of
+    ``solve_batch_arrays(solution=True)`` and its kin; n and m are that LP's own."""
+    return Solution(arrays["x"][index][:m].copy(), arrays["duals"][index][:n].copy(),
+                    float(arrays["objective"][index]), arrays["basis"][index][:n].copy(),
+                    arrays["nonbasis"][index][:m].copy(), int(arrays["npivots"][index]))
+
+
+def _fallback(cons, func, max_pivots, history):
+    try:
+        sm = SimplexMethod(cons, func)
+        if history:
+            return sm.get_solution(max_pivots=max_pivots), sm.status
+        return sm.solve(record_history=False, max_pivots=max_pivots), sm.status
+    except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
+        return exc, "exception"
+
+
+def _fallback_answer(cons, func, max_pivots, answer):
+    """One problem through ``SimplexMethod``; ``answer`` is the method that reads the result off
+    the solved object (``SimplexMethod.solution`` / ``.ranging``)."""
+    try:
+        sm = SimplexMethod(cons, func)
+        sm.solve(record_history=False, max_pivots=max_pivots)
+        return answer(sm), sm.status
+    except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
+        return exc, "exception"
+
+
+def _drive(problems, kernel, max_pivots, history, single, launch):
+    """The scaffold of every object-level call: refuse a ``kernel`` that is no name and a machine
+    without a device, route the problems (``_routes``), have ``single(k, constraints, function)``
+    answer those routed ``"single"`` and ``launch(tier, idx, tabs, dims)`` every launch of the
+    rest (``_launches``, ``pack``; problem ``idx[q]`` is member q).  Both store their answers
+    themselves, by problem index."""
+    _kernel_name(kernel)
+    _need_device()
+    routes = _routes(problems, kernel)
+    for k, (c, f) in enumerate(problems):
+        if routes[k] == "single":
+            single(k, c, f)
+    for which, idx in _launches(problems, routes, max_pivots, history):
+        tabs, dims = pack([problems[k] for k in idx])
+        launch(which, idx, tabs, dims)
+
+
 def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=None,
                 kernel: str = "auto"):
     """Solve every ``(constraints, function)``; returns ``(results, statuses)``.
@@ -430,20 +573,14 @@ def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=No
     global problems to ``SimplexMethod``.  ``kernel="global"`` sends the wave and workgroup
     problems through the global-memory kernel too, whatever their number."""
     problems = list(problems)
-    if kernel not in KERNELS:
-        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
     results = [None] * len(problems)
     statuses = [None] * len(problems)
-    routes = _routes(problems, kernel)
-    for k, (c, f) in enumerate(problems):
-        if routes[k] == "single":
-            results[k], statuses[k] = _fallback(c, f, max_pivots, history)
-    launches = _launches(problems, routes, max_pivots, history)
     P = int(max_pivots)
-    for which, idx in launches:
-        tabs, dims = pack([problems[k] for k in idx])
+
+    def single(k, c, f):
+        results[k], statuses[k] = _fallback(c, f, max_pivots, history)
+
+    def launch(which, idx, tabs, dims):
         out = solve_batch_arrays(tabs, dims, max_pivots, history, device, kernel=which)
         # Hundreds of thousands of fresh, acyclic lists: pause the cyclic collector while they
         # are built, or its generational passes rescan the growing result set (5x slower at 20k
@@ -459,16 +596,31 @@ def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=No
         finally:
             if gc_was_on:
                 gc.enable()
+
+    _drive(problems, kernel, max_pivots, history, single, launch)
     return results, statuses
 
 
-def _fallback_solution(cons, func, max_pivots):
-    try:
-        sm = SimplexMethod(cons, func)
-        sm.solve(record_history=False, max_pivots=max_pivots)
-        return sm.solution(), sm.status
-    except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
-        return exc, "exception"
+def _solve_batch_answers(problems, max_pivots, device, kernel, answer, ranging, at):
+    """``solve_batch_solutions`` and ``solve_batch_ranges``: ``answer`` reads a fallback's result
+    off its ``SimplexMethod``, ``at(arrays, q, n, m)`` a launch member's off the arrays."""
+    problems = list(problems)
+    results = [None] * len(problems)
+    statuses = [None] * len(problems)
+    P = int(max_pivots)
+
+    def single(k, c, f):
+        results[k], statuses[k] = _fallback_answer(c, f, max_pivots, answer)
+
+    def launch(which, idx, tabs, dims):
+        out = solve_batch_arrays(tabs, dims, max_pivots, False, device, kernel=which,
+                                 solution=True, tables=False, ranging=ranging)
+        for q, k in enumerate(idx):
+            results[k] = at(out, q, int(dims[q, 0]), int(dims[q, 1]))
+            statuses[k] = _status_name(int(out["status"][q]), int(out["npivots"][q]), P)
+
+    _drive(problems, kernel, max_pivots, False, single, launch)
+    return results, statuses
 
 
 def solve_batch_solutions(problems, max_pivots: int = 256, device=None, kernel: str = "auto"):
@@ -482,46 +634,13 @@ def solve_batch_solutions(problems, max_pivots: int = 256, device=None, kernel: 
     the status.  Routing and launch splitting are ``solve_batch``'s; of a launch only the
     solutions come back from the device (``solve_batch_arrays(solution=True, tables=False)``),
     and no ``Info`` objects are built."""
-    problems = list(problems)
-    if kernel not in KERNELS:
-        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
-    results = [None] * len(problems)
-    statuses = [None] * len(problems)
-    routes = _routes(problems, kernel)
-    for k, (c, f) in enumerate(problems):
-        if routes[k] == "single":
-            results[k], statuses[k] = _fallback_solution(c, f, max_pivots)
-    P = int(max_pivots)
-    for which, idx in _launches(problems, routes, max_pivots, False):
-        tabs, dims = pack([problems[k] for k in idx])
-        out = solve_batch_arrays(tabs, dims, max_pivots, False, device, kernel=which,
-                                 solution=True, tables=False)
-        for q, k in enumerate(idx):
-            n, m = int(dims[q, 0]), int(dims[q, 1])
-            status, np_ = int(out["status"][q]), int(out["npivots"][q])
-            results[k] = Solution(out["x"][q, :m].copy(), out["duals"][q, :n].copy(),
-                                  float(out["objective"][q]), out["basis"][q, :n].copy(),
-                                  out["nonbasis"][q, :m].copy(), np_)
-            if status == _lib.OPTIMUM:
-                statuses[k] = "optimum"
-            elif status in MESSAGES:
-                statuses[k] = "error"
-            elif status == _lib.PIVOT and np_ >= P:
-                statuses[k] = "cap"
-            else:
-                raise RuntimeError(f"unexpected batch status {status}")
-    return results, statuses
+    return _solve_batch_answers(problems, max_pivots, device, kernel, SimplexMethod.solution,
+                                False, _solution_at)
 
 
-def _fallback_ranging(cons, func, max_pivots):
-    try:
-        sm = SimplexMethod(cons, func)
-        sm.solve(record_history=False, max_pivots=max_pivots)
-        return sm.ranging(), sm.status
-    except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
-        return exc, "exception"
+def _ranging_at(arrays, q, n, m):
+    return Ranging(arrays["rhs_lo"][q, :n].copy(), arrays["rhs_hi"][q, :n].copy(),
+                   arrays["cost_lo"][q, :m].copy(), arrays["cost_hi"][q, :m].copy())
 
 
 def solve_batch_ranges(problems, max_pivots: int = 256, device=None, kernel: str = "auto"):
@@ -534,79 +653,56 @@ def solve_batch_ranges(problems, max_pivots: int = 256, device=None, kernel: str
     ``statuses[k]`` as in ``solve_batch``.  The values stand whatever the status.  Routing and
     launch splitting are ``solve_batch``'s; of a launch only the solutions and the ranges come
     back from the device (``solve_batch_arrays(solution=True, ranging=True, tables=False)``)."""
-    problems = list(problems)
-    if kernel not in KERNELS:
-        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
-    results = [None] * len(problems)
-    statuses = [None] * len(problems)
-    routes = _routes(problems, kernel)
-    for k, (c, f) in enumerate(problems):
-        if routes[k] == "single":
-            results[k], statuses[k] = _fallback_ranging(c, f, max_pivots)
-    P = int(max_pivots)
-    for which, idx in _launches(problems, routes, max_pivots, False):
-        tabs, dims = pack([problems[k] for k in idx])
-        out = solve_batch_arrays(tabs, dims, max_pivots, False, device, kernel=which,
-                                 solution=True, tables=False, ranging=True)
-        for q, k in enumerate(idx):
-            n, m = int(dims[q, 0]), int(dims[q, 1])
-            results[k] = Ranging(out["rhs_lo"][q, :n].copy(), out["rhs_hi"][q, :n].copy(),
-                                 out["cost_lo"][q, :m].copy(), out["cost_hi"][q, :m].copy())
-            statuses[k] = _status_name(int(out["status"][q]), int(out["npivots"][q]), P)
-    return results, statuses
+    return _solve_batch_answers(problems, max_pivots, device, kernel, SimplexMethod.ranging,
+                                True, _ranging_at)
 
 
-def _device_solution(L, stream, dev, d_final, d_dims, B, Rmax, ldb, P, d_rc, d_np, d_func,
-                     start=None):
-    """Enqueue smx_batch_solution (``start`` = (basis0, nonbasis0, group): smx_batch_solution_from)
-    on fresh outputs; returns the device tensors (x, duals, objective, basis, nonbasis)."""
-    d_x = torch.empty((B, ldb), dtype=torch.float64, device=dev)
-    d_du = torch.empty((B, Rmax), dtype=torch.float64, device=dev)
-    d_obj = torch.empty(B, dtype=torch.float64, device=dev)
-    d_ba = torch.empty((B, Rmax), dtype=torch.int32, device=dev)
-    d_nb = torch.empty((B, ldb), dtype=torch.int32, device=dev)
-    head = (d_final.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, P, d_rc.data_ptr(),
-            d_np.data_ptr(), d_func.data_ptr())
-    tail = (d_x.data_ptr(), d_du.data_ptr(), d_obj.data_ptr(), d_ba.data_ptr(), d_nb.data_ptr(),
-            stream.cuda_stream)
-    if start is None:
-        _lib.check(L.smx_batch_solution(*head, *tail), "smx_batch_solution")
-    else:
-        _lib.check(L.smx_batch_solution_from(*head, start[0].data_ptr(), start[1].data_ptr(),
-                                             int(start[2]), *tail), "smx_batch_solution_from")
-    return d_x, d_du, d_obj, d_ba, d_nb
-
-
-def _device_ranging(L, stream, dev, d_final, d_dims, B, Rmax, ldb, d_ba, d_nb):
-    """Enqueue smx_batch_ranging on fresh outputs; returns (rhs_lo, rhs_hi, cost_lo, cost_hi)."""
-    d_rl, d_rh = (torch.empty((B, Rmax), dtype=torch.float64, device=dev) for _ in "lh")
-    d_cl, d_ch = (torch.empty((B, ldb), dtype=torch.float64, device=dev) for _ in "lh")
-    _lib.check(L.smx_batch_ranging(
-        d_final.data_ptr(), d_dims.data_ptr(), B, Rmax, ldb, d_ba.data_ptr(), d_nb.data_ptr(),
-        d_rl.data_ptr(), d_rh.data_ptr(), d_cl.data_ptr(), d_ch.data_ptr(), stream.cuda_stream),
-        "smx_batch_ranging")
-    return d_rl, d_rh, d_cl, d_ch
-
-
-def _solution_arrays(sol, Rmax, ldb, lead):
-    """The host arrays of a ``_device_solution`` result, cut like ``solve_batch_arrays`` cuts
-    them and reshaped to ``lead`` + [...]."""
-    d_x, d_du, d_obj, d_ba, d_nb = sol
-    return {"x": d_x[:, :ldb - 1].contiguous().cpu().numpy().reshape(*lead, ldb - 1),
-            "duals": d_du[:, :Rmax - 1].contiguous().cpu().numpy().reshape(*lead, Rmax - 1),
-            "objective": d_obj.cpu().numpy().reshape(*lead),
-            "basis": d_ba[:, :Rmax - 1].contiguous().cpu().numpy().reshape(*lead, Rmax - 1),
-            "nonbasis": d_nb[:, :ldb - 1].contiguous().cpu().numpy().reshape(*lead, ldb - 1)}
-
-
-def _ranging_arrays(rng, Rmax, ldb, lead):
-    d_rl, d_rh, d_cl, d_ch = rng
-    return {"rhs_lo": d_rl[:, :Rmax - 1].contiguous().cpu().numpy().reshape(*lead, Rmax - 1),
-            "rhs_hi": d_rh[:, :Rmax - 1].contiguous().cpu().numpy().reshape(*lead, Rmax - 1),
-            "cost_lo": d_cl[:, :ldb - 1].contiguous().cpu().numpy().reshape(*lead, ldb - 1),
-            "cost_hi": d_ch[:, :ldb - 1].contiguous().cpu().numpy().reshape(*lead, ldb - 1)}
+def _warm_chain(L, dev, tabs, dims, tier, P, S, make, rows, warm_tier, Pw, ranging, log):
+    """The chain of both warm calls, on one stream and with no host round trip between the steps:
+    the base launch of ``tabs`` / ``dims`` on ``tier`` (``_enqueue_base``), then for every slice of
+    the S sets ``make(stream, s0, c, final, d_dims, func, basis, nonbasis)``, which enqueues the
+    kernel that writes the B * c warm tables of sets s0..s0 + c - 1 (``rows`` rows each) from the
+    base launch's device tensors and returns (tables, their dims, their function rows, the
+    ``start`` of ``_device_solution``); the warm solve on ``warm_tier`` capped at ``Pw``, its
+    solution from ``start`` and, with ``ranging``, its ranges.  A slice holds as many sets as keep
+    its tables under ``GM_TABLE_BUDGET``.  Only when everything is enqueued does anything come
+    back: ``base`` (``_base_arrays``) and per set, shaped [B][S]..., ``status``, ``npivots``, with
+    ``log`` the warm pivot log ``rc``, the solution arrays and with ``ranging`` the range arrays.
+    S == 0 runs one slice of no sets, on which every library call returns at once, so that its
+    result has the shapes of any other."""
+    B, _, ldb = tabs.shape
+    per = max(1, min(S, GM_TABLE_BUDGET // max(1, B * rows * ldb * 8)))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        d_tabs = torch.from_numpy(tabs).to(dev)
+        d_dims = torch.from_numpy(dims).to(dev)
+        run, d_func, sol, rng = _enqueue_base(L, stream, tier, d_tabs, d_dims, P, ranging=ranging)
+        slices = []
+        for s0 in range(0, S, per) or (0,):                  # S == 0: one slice, of no sets
+            c = min(S, s0 + per) - s0
+            d_wtabs, d_wdims, d_wfunc, start = make(stream, s0, c, run[0], d_dims, d_func,
+                                                    sol[3], sol[4])
+            d_wout, d_wrc, _, d_wst, d_wnp, _ = _device_solve(L, stream, warm_tier, d_wtabs,
+                                                              d_wdims, Pw)
+            wsol = _device_solution(L, stream, d_wout, d_wdims, Pw, d_wrc, d_wnp, d_wfunc, start)
+            wrng = _device_ranging(L, stream, d_wout, d_wdims, wsol[3], wsol[4]) if ranging else ()
+            slices.append((c, d_wst, d_wnp, d_wrc if log else None, wsol, wrng))
+            del d_wtabs, d_wout, d_wrc               # a slice's tables do not outlive it
+        # everything is enqueued: only now does anything come back
+        res = {"base": _base_arrays(run, sol, rng)}
+        parts = []
+        for c, d_wst, d_wnp, d_wrc, wsol, wrng in slices:
+            part = {"status": d_wst.cpu().numpy().reshape(B, c),
+                    "npivots": d_wnp.cpu().numpy().reshape(B, c)}
+            if log:
+                part["rc"] = d_wrc.cpu().numpy().reshape(B, c, max(Pw, 1), 2)
+            part.update(_solution_arrays(wsol, (B, c)))
+            if ranging:
+                part.update(_ranging_arrays(wrng, (B, c)))
+            parts.append(part)
+    for key in parts[0]:
+        res[key] = np.concatenate([p[key] for p in parts], axis=1)
+    return res
 
 
 def solve_batch_scenarios_arrays(tabs: np.ndarray, dims: np.ndarray, drhs: np.ndarray,
@@ -631,26 +727,17 @@ def solve_batch_scenarios_arrays(tabs: np.ndarray, dims: np.ndarray, drhs: np.nd
     ``nonbasis`` and with ``ranging`` the four range arrays.  A warm run need not terminate where
     a cold solve of the perturbed problem would (the selection rule is no dual simplex): read
     ``status``; SMX_PIVOT there means ``warm_pivots`` was reached."""
-    if kernel not in KERNELS:
-        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
-    tabs = np.ascontiguousarray(tabs, dtype=np.float64)
-    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    _kernel_name(kernel)
     drhs = np.ascontiguousarray(drhs, dtype=np.float64)
     dcost = np.ascontiguousarray(dcost, dtype=np.float64)
-    B, Rmax, ldb = tabs.shape
-    if dims.shape != (B, 3):
-        raise ValueError("dims must be int32 [B][3]")
+    tabs, dims, (B, Rmax, ldb) = _launch_arrays(tabs, dims)
     if drhs.ndim != 3 or drhs.shape[0] != B or drhs.shape[2] != Rmax - 1:
         raise ValueError("drhs must be float64 [B][S][Rmax - 1]")
     S = drhs.shape[1]
     if dcost.shape != (B, S, ldb - 1):
         raise ValueError("dcost must be float64 [B][S][ldb - 1]")
-    if not torch.cuda.is_available():
-        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
-    which = choose_kernel(Rmax, ldb, kernel) if B else "wave"
-    if B and ((dims[:, 0] + 1 > Rmax).any() or (dims[:, 1] + 1 > ldb).any() or
-              (dims[:, 1] < 1).any() or (dims[:, 0] < 1).any()):
-        raise ValueError(ENVELOPE_ERROR)
+    _need_device()
+    which = _launch_tier(dims, (B, Rmax, ldb), kernel)
     if solution_lds_bytes(Rmax, ldb) < 0 or not scenario_fits(Rmax, ldb):
         raise ValueError(ENVELOPE_ERROR)
     if ranging and not ranging_fits(Rmax, ldb):
@@ -658,88 +745,33 @@ def solve_batch_scenarios_arrays(tabs: np.ndarray, dims: np.ndarray, drhs: np.nd
     P = int(max_pivots)
     Pw = P if warm_pivots is None else int(warm_pivots)
     L = _lib.load()
-    solve, what = {"wave": (L.smx_batch_solve, "smx_batch_solve"),
-                   "workgroup": (L.smx_batch_solve_wg, "smx_batch_solve_wg"),
-                   "global": (L.smx_batch_solve_gm, "smx_batch_solve_gm")}[which]
     # the deltas in the kernel's layout: rows of Rmax / ldb, the last entry unused
     h_dr = np.zeros((B, S, Rmax), dtype=np.float64)
     h_dr[:, :, :Rmax - 1] = drhs
     h_dc = np.zeros((B, S, ldb), dtype=np.float64)
     h_dc[:, :, :ldb - 1] = dcost
-    per = max(1, min(S, GM_TABLE_BUDGET // max(1, B * Rmax * ldb * 8)))
     dev = torch.device(device if device is not None else "cuda")
-
-    def run(d_in, d_dims_, count, cap):
-        d_out = torch.empty_like(d_in)
-        d_rc = torch.zeros((count, max(cap, 1), 2), dtype=torch.int32, device=dev)
-        d_xv = torch.zeros((count, max(cap, 1), 2), dtype=torch.float64, device=dev)
-        d_st = torch.zeros(count, dtype=torch.int32, device=dev)
-        d_np = torch.zeros(count, dtype=torch.int32, device=dev)
-        _lib.check(solve(d_in.data_ptr(), d_dims_.data_ptr(), count, Rmax, ldb, cap,
-                         d_out.data_ptr(), d_rc.data_ptr(), d_xv.data_ptr(), None,
-                         d_st.data_ptr(), d_np.data_ptr(), stream.cuda_stream), what)
-        return d_out, d_rc, d_xv, d_st, d_np
-
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        d_tabs = torch.from_numpy(tabs).to(dev)
-        d_dims = torch.from_numpy(dims).to(dev)
         d_dr = torch.from_numpy(h_dr).to(dev)
         d_dc = torch.from_numpy(h_dc).to(dev)
-        d_out, d_rc, d_xv, d_st, d_np = run(d_tabs, d_dims, B, P)
-        d_func = d_tabs[torch.arange(B, device=dev), d_dims[:, 0].long()].contiguous()
-        sol = _device_solution(L, stream, dev, d_out, d_dims, B, Rmax, ldb, P, d_rc, d_np, d_func)
-        rng = (_device_ranging(L, stream, dev, d_out, d_dims, B, Rmax, ldb, sol[3], sol[4])
-               if ranging else None)
-        slices = []
-        for s0 in range(0, S, per):
-            c = min(S, s0 + per) - s0
-            Q = B * c
-            d_ts = torch.empty((Q, Rmax, ldb), dtype=torch.float64, device=dev)
-            d_fs = torch.empty((Q, ldb), dtype=torch.float64, device=dev)
-            d_ds = torch.empty((Q, 3), dtype=torch.int32, device=dev)
-            d_drs = d_dr[:, s0:s0 + c].contiguous()          # named: alive until the launch
-            d_dcs = d_dc[:, s0:s0 + c].contiguous()
-            _lib.check(L.smx_batch_scenario(
-                d_out.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, sol[3].data_ptr(),
-                sol[4].data_ptr(), d_func.data_ptr(), d_drs.data_ptr(), d_dcs.data_ptr(),
-                d_ts.data_ptr(), d_fs.data_ptr(), d_ds.data_ptr(), stream.cuda_stream),
-                "smx_batch_scenario")
-            d_wout, d_wrc, _, d_wst, d_wnp = run(d_ts, d_ds, Q, Pw)
-            wsol = _device_solution(L, stream, dev, d_wout, d_ds, Q, Rmax, ldb, Pw, d_wrc, d_wnp,
-                                    d_fs, start=(sol[3], sol[4], c))
-            wrng = (_device_ranging(L, stream, dev, d_wout, d_ds, Q, Rmax, ldb, wsol[3], wsol[4])
-                    if ranging else None)
-            slices.append((c, d_wst, d_wnp, wsol, wrng))
-            del d_ts, d_wout, d_wrc
-        # everything is enqueued: only now does anything come back
-        base = {"rc": d_rc.cpu().numpy(), "xv": d_xv.cpu().numpy(),
-                "status": d_st.cpu().numpy(), "npivots": d_np.cpu().numpy()}
-        base.update(_solution_arrays(sol, Rmax, ldb, (B,)))
-        if ranging:
-            base.update(_ranging_arrays(rng, Rmax, ldb, (B,)))
-        parts = []
-        for c, d_wst, d_wnp, wsol, wrng in slices:
-            part = {"status": d_wst.cpu().numpy().reshape(B, c),
-                    "npivots": d_wnp.cpu().numpy().reshape(B, c)}
-            part.update(_solution_arrays(wsol, Rmax, ldb, (B, c)))
-            if ranging:
-                part.update(_ranging_arrays(wrng, Rmax, ldb, (B, c)))
-            parts.append(part)
-    res = {"base": base}
-    if parts:
-        for key in parts[0]:
-            res[key] = np.concatenate([p[key] for p in parts], axis=1)
-    else:                                                    # S == 0
-        res.update({"status": np.zeros((B, 0), np.int32), "npivots": np.zeros((B, 0), np.int32),
-                    "x": np.zeros((B, 0, ldb - 1)), "duals": np.zeros((B, 0, Rmax - 1)),
-                    "objective": np.zeros((B, 0)),
-                    "basis": np.zeros((B, 0, Rmax - 1), np.int32),
-                    "nonbasis": np.zeros((B, 0, ldb - 1), np.int32)})
-        if ranging:
-            res.update({"rhs_lo": np.zeros((B, 0, Rmax - 1)), "rhs_hi": np.zeros((B, 0, Rmax - 1)),
-                        "cost_lo": np.zeros((B, 0, ldb - 1)), "cost_hi": np.zeros((B, 0, ldb - 1))})
-    return res
+
+    def make(stream, s0, c, d_final, d_dims, d_func, d_basis, d_nonbasis):
+        Q = B * c
+        d_ts = torch.empty((Q, Rmax, ldb), dtype=torch.float64, device=dev)
+        d_fs = torch.empty((Q, ldb), dtype=torch.float64, device=dev)
+        d_ds = torch.empty((Q, 3), dtype=torch.int32, device=dev)
+        d_drs = d_dr[:, s0:s0 + c].contiguous()              # named: alive until the launch
+        d_dcs = d_dc[:, s0:s0 + c].contiguous()
+        _lib.check(L.smx_batch_scenario(
+            d_final.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, d_basis.data_ptr(),
+            d_nonbasis.data_ptr(), d_func.data_ptr(), d_drs.data_ptr(), d_dcs.data_ptr(),
+            d_ts.data_ptr(), d_fs.data_ptr(), d_ds.data_ptr(), stream.cuda_stream),
+            "smx_batch_scenario")
+        # the labels carry on from the base LP's: table q starts from those of LP q / c (a slice
+        # of no sets still names a legal group)
+        return d_ts, d_ds, d_fs, (d_basis, d_nonbasis, max(c, 1))
+
+    return _warm_chain(L, dev, tabs, dims, which, P, S, make, Rmax, which, Pw, ranging, False)
 
 
 def _perturbed(cons, func, drhs, dcost):
@@ -757,19 +789,41 @@ def _perturbed(cons, func, drhs, dcost):
     return cons, func
 
 
-def _fallback_scenarios(cons, func, scen, max_pivots, warm_pivots):
+def _fallback_warm(cons, func, sets, max_pivots, warm_pivots, successor):
+    """One problem and its sets through ``SimplexMethod``; ``successor(sm, set)`` is the warm
+    object of a set (``what_if`` / ``add_constraints``)."""
     try:
         sm = SimplexMethod(cons, func)
         sm.solve(record_history=False, max_pivots=max_pivots)
         base = sm.solution()
         out = []
-        for drhs, dcost in scen:
-            wi = sm.what_if(drhs, dcost)
-            wi.solve(record_history=False, max_pivots=warm_pivots)
-            out.append(Scenario(wi.solution(), wi.status, True))
+        for entry in sets:
+            warm = successor(sm, entry)
+            warm.solve(record_history=False, max_pivots=warm_pivots)
+            out.append(Scenario(warm.solution(), warm.status, True))
         return base, out
     except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
-        return exc, [Scenario(exc, "exception", True) for _ in scen]
+        return exc, [Scenario(exc, "exception", True) for _ in sets]
+
+
+def _warm_answers(out, q, n, m, added, Pw):
+    """(Solution, [Scenario]) of member q of a warm launch; set s holds n + added[s] rows."""
+    return (_solution_at(out["base"], q, n, m),
+            [Scenario(_solution_at(out, (q, s), n + a, m),
+                      _status_name(int(out["status"][q, s]), int(out["npivots"][q, s]), Pw), True)
+             for s, a in enumerate(added)])
+
+
+def _cold_tail(results, cold_problem, max_pivots, device, kernel):
+    """``cold_fallback``: every set whose warm run did not end at an optimum is solved cold, as
+    the problem ``cold_problem(k, s)``, through ``solve_batch_solutions``."""
+    todo = [(k, s) for k, (_, answers) in enumerate(results) for s, sc in enumerate(answers)
+            if sc.status not in ("optimum", "exception")]
+    if todo:
+        sols, sts = solve_batch_solutions([cold_problem(k, s) for k, s in todo], max_pivots,
+                                          device, kernel)
+        for (k, s), sol, st in zip(todo, sols, sts):
+            results[k][1][s] = Scenario(sol, st, False)
 
 
 def solve_batch_scenarios(problems, scenarios, max_pivots: int = 256, warm_pivots=None,
@@ -789,21 +843,17 @@ def solve_batch_scenarios(problems, scenarios, max_pivots: int = 256, warm_pivot
     with the full ``max_pivots`` and marked ``warm=False``."""
     problems = list(problems)
     scenarios = [list(s) for s in scenarios]
-    if kernel not in KERNELS:
-        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    _kernel_name(kernel)                                     # refused before the scenarios are
     if len(scenarios) != len(problems):
         raise ValueError("scenarios must hold one list of scenarios per problem")
-    if not torch.cuda.is_available():
-        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
     P = int(max_pivots)
     Pw = P if warm_pivots is None else int(warm_pivots)
     results = [None] * len(problems)
-    routes = _routes(problems, kernel)
-    for k, (c, f) in enumerate(problems):
-        if routes[k] == "single":
-            results[k] = _fallback_scenarios(c, f, scenarios[k], P, Pw)
-    for which, idx in _launches(problems, routes, max_pivots, False):
-        tabs, dims = pack([problems[k] for k in idx])
+
+    def single(k, c, f):
+        results[k] = _fallback_warm(c, f, scenarios[k], P, Pw, lambda sm, sc: sm.what_if(*sc))
+
+    def launch(which, idx, tabs, dims):
         _, Rmax, ldb = tabs.shape
         S = max(len(scenarios[k]) for k in idx)
         drhs = np.zeros((len(idx), S, Rmax - 1), dtype=np.float64)
@@ -816,38 +866,15 @@ def solve_batch_scenarios(problems, scenarios, max_pivots: int = 256, warm_pivot
                 if dc is not None:
                     dcost[q, s, :m] = np.asarray(dc, dtype=np.float64).reshape(m)
         out = solve_batch_scenarios_arrays(tabs, dims, drhs, dcost, P, Pw, device, kernel=which)
-        base = out["base"]
         for q, k in enumerate(idx):
-            n, m = int(dims[q, 0]), int(dims[q, 1])
-            sol = Solution(base["x"][q, :m].copy(), base["duals"][q, :n].copy(),
-                           float(base["objective"][q]), base["basis"][q, :n].copy(),
-                           base["nonbasis"][q, :m].copy(), int(base["npivots"][q]))
-            scen = []
-            for s in range(len(scenarios[k])):
-                np_ = int(out["npivots"][q, s])
-                scen.append(Scenario(
-                    Solution(out["x"][q, s, :m].copy(), out["duals"][q, s, :n].copy(),
-                             float(out["objective"][q, s]), out["basis"][q, s, :n].copy(),
-                             out["nonbasis"][q, s, :m].copy(), np_),
-                    _status_name(int(out["status"][q, s]), np_, Pw), True))
-            results[k] = (sol, scen)
+            results[k] = _warm_answers(out, q, int(dims[q, 0]), int(dims[q, 1]),
+                                       [0] * len(scenarios[k]), Pw)
+
+    _drive(problems, kernel, max_pivots, False, single, launch)
     if cold_fallback:
-        todo = [(k, s) for k, (_, scen) in enumerate(results) for s, sc in enumerate(scen)
-                if sc.status not in ("optimum", "exception")]
-        if todo:
-            cold = [_perturbed(*problems[k], *scenarios[k][s]) for k, s in todo]
-            sols, sts = solve_batch_solutions(cold, max_pivots, device, kernel)
-            for (k, s), sol, st in zip(todo, sols, sts):
-                results[k][1][s] = Scenario(sol, st, False)
+        _cold_tail(results, lambda k, s: _perturbed(*problems[k], *scenarios[k][s]), max_pivots,
+                   device, kernel)
     return results
-
-
-def cuts_fits(Rmax_out: int, ldb: int) -> bool:
-    """Whether output blocks of Rmax_out x ldb are inside k_batch_cuts's envelope (the library is
-    the one source of the rule)."""
-    if not (0 <= Rmax_out < 1 << 31 and 0 <= ldb < 1 << 31):
-        return False
-    return bool(_lib.load().smx_batch_cuts_fits(int(Rmax_out), int(ldb)))
 
 
 _TIERS = ("wave", "workgroup", "global")
@@ -893,15 +920,10 @@ def solve_batch_cuts_arrays(tabs: np.ndarray, dims: np.ndarray, cuts: np.ndarray
     A new constraint's label code is m_k + n_k + c.  A warm run need not terminate where a cold
     solve of the enlarged problem would (the selection rule is no dual simplex): read ``status``;
     SMX_PIVOT there means ``warm_pivots`` was reached."""
-    if kernel not in KERNELS:
-        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
-    tabs = np.ascontiguousarray(tabs, dtype=np.float64)
-    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    _kernel_name(kernel)
     cuts = np.ascontiguousarray(cuts, dtype=np.float64)
     ncuts = np.ascontiguousarray(ncuts, dtype=np.int32)
-    B, Rmax, ldb = tabs.shape
-    if dims.shape != (B, 3):
-        raise ValueError("dims must be int32 [B][3]")
+    tabs, dims, (B, Rmax, ldb) = _launch_arrays(tabs, dims)
     if cuts.ndim != 4 or cuts.shape[0] != B or cuts.shape[3] != ldb:
         raise ValueError("cuts must be float64 [B][S][K][ldb]")
     S, K = cuts.shape[1], cuts.shape[2]
@@ -909,14 +931,10 @@ def solve_batch_cuts_arrays(tabs: np.ndarray, dims: np.ndarray, cuts: np.ndarray
         raise ValueError("ncuts must be int32 [B][S]")
     if ((ncuts < 0) | (ncuts > K)).any():
         raise ValueError("ncuts must lie in 0..K")
-    if not torch.cuda.is_available():
-        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
+    _need_device()
     Rout = Rmax + K
-    which = choose_kernel(Rmax, ldb, kernel) if B else "wave"
+    which = _launch_tier(dims, (B, Rmax, ldb), kernel)
     warm = warm_kernel(which, Rout, ldb) if B else "wave"
-    if B and ((dims[:, 0] + 1 > Rmax).any() or (dims[:, 1] + 1 > ldb).any() or
-              (dims[:, 1] < 1).any() or (dims[:, 0] < 1).any()):
-        raise ValueError(ENVELOPE_ERROR)
     if solution_lds_bytes(Rout, ldb) < 0 or not cuts_fits(Rout, ldb):
         raise ValueError(ENVELOPE_ERROR)
     if ranging and not ranging_fits(Rout, ldb):
@@ -924,111 +942,33 @@ def solve_batch_cuts_arrays(tabs: np.ndarray, dims: np.ndarray, cuts: np.ndarray
     P = int(max_pivots)
     Pw = P if warm_pivots is None else int(warm_pivots)
     L = _lib.load()
-    solvers = {"wave": (L.smx_batch_solve, "smx_batch_solve"),
-               "workgroup": (L.smx_batch_solve_wg, "smx_batch_solve_wg"),
-               "global": (L.smx_batch_solve_gm, "smx_batch_solve_gm")}
-    per = max(1, min(S, GM_TABLE_BUDGET // max(1, B * Rout * ldb * 8)))
     dev = torch.device(device if device is not None else "cuda")
-
-    def run(tier, d_in, d_dims_, count, rows, cap):
-        solve, what = solvers[tier]
-        d_out = torch.empty_like(d_in)
-        d_rc = torch.zeros((count, max(cap, 1), 2), dtype=torch.int32, device=dev)
-        d_xv = torch.zeros((count, max(cap, 1), 2), dtype=torch.float64, device=dev)
-        d_st = torch.zeros(count, dtype=torch.int32, device=dev)
-        d_np = torch.zeros(count, dtype=torch.int32, device=dev)
-        _lib.check(solve(d_in.data_ptr(), d_dims_.data_ptr(), count, rows, ldb, cap,
-                         d_out.data_ptr(), d_rc.data_ptr(), d_xv.data_ptr(), None,
-                         d_st.data_ptr(), d_np.data_ptr(), stream.cuda_stream), what)
-        return d_out, d_rc, d_xv, d_st, d_np
-
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        d_tabs = torch.from_numpy(tabs).to(dev)
-        d_dims = torch.from_numpy(dims).to(dev)
         d_cuts = torch.from_numpy(cuts).to(dev)
         d_nc = torch.from_numpy(ncuts).to(dev)
-        d_out, d_rc, d_xv, d_st, d_np = run(which, d_tabs, d_dims, B, Rmax, P)
-        d_func = d_tabs[torch.arange(B, device=dev), d_dims[:, 0].long()].contiguous()
-        sol = _device_solution(L, stream, dev, d_out, d_dims, B, Rmax, ldb, P, d_rc, d_np, d_func)
-        rng = (_device_ranging(L, stream, dev, d_out, d_dims, B, Rmax, ldb, sol[3], sol[4])
-               if ranging else None)
-        slices = []
-        for s0 in range(0, S, per):
-            c = min(S, s0 + per) - s0
-            Q = B * c
-            d_tc = torch.empty((Q, Rout, ldb), dtype=torch.float64, device=dev)
-            d_dc = torch.empty((Q, 3), dtype=torch.int32, device=dev)
-            d_bc = torch.empty((Q, Rout), dtype=torch.int32, device=dev)
-            d_cs = d_cuts[:, s0:s0 + c].contiguous()         # named: alive until the launch
-            d_ns = d_nc[:, s0:s0 + c].contiguous()
-            _lib.check(L.smx_batch_cuts(
-                d_out.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, sol[3].data_ptr(),
-                sol[4].data_ptr(), d_cs.data_ptr() if K else None, d_ns.data_ptr(), K, Rout,
-                d_tc.data_ptr(), d_dc.data_ptr(), d_bc.data_ptr(), stream.cuda_stream),
-                "smx_batch_cuts")
-            d_wout, d_wrc, _, d_wst, d_wnp = run(warm, d_tc, d_dc, Q, Rout, Pw)
-            # every table's own start labels (group 1): its LP's column labels and function row
-            d_n0 = sol[4].repeat_interleave(c, dim=0)
-            d_fq = d_func.repeat_interleave(c, dim=0)
-            wsol = _device_solution(L, stream, dev, d_wout, d_dc, Q, Rout, ldb, Pw, d_wrc, d_wnp,
-                                    d_fq, start=(d_bc, d_n0, 1))
-            wrng = (_device_ranging(L, stream, dev, d_wout, d_dc, Q, Rout, ldb, wsol[3], wsol[4])
-                    if ranging else None)
-            slices.append((c, d_wst, d_wnp, d_wrc, wsol, wrng))
-            del d_tc, d_wout
-        # everything is enqueued: only now does anything come back
-        base = {"rc": d_rc.cpu().numpy(), "xv": d_xv.cpu().numpy(),
-                "status": d_st.cpu().numpy(), "npivots": d_np.cpu().numpy()}
-        base.update(_solution_arrays(sol, Rmax, ldb, (B,)))
-        if ranging:
-            base.update(_ranging_arrays(rng, Rmax, ldb, (B,)))
-        parts = []
-        for c, d_wst, d_wnp, d_wrc, wsol, wrng in slices:
-            part = {"status": d_wst.cpu().numpy().reshape(B, c),
-                    "npivots": d_wnp.cpu().numpy().reshape(B, c)}
-            if log:
-                part["rc"] = d_wrc.cpu().numpy().reshape(B, c, max(Pw, 1), 2)
-            part.update(_solution_arrays(wsol, Rout, ldb, (B, c)))
-            if ranging:
-                part.update(_ranging_arrays(wrng, Rout, ldb, (B, c)))
-            parts.append(part)
-    res = {"base": base}
-    if parts:
-        for key in parts[0]:
-            res[key] = np.concatenate([p[key] for p in parts], axis=1)
-    else:                                                    # S == 0
-        res.update({"status": np.zeros((B, 0), np.int32), "npivots": np.zeros((B, 0), np.int32),
-                    "x": np.zeros((B, 0, ldb - 1)), "duals": np.zeros((B, 0, Rout - 1)),
-                    "objective": np.zeros((B, 0)),
-                    "basis": np.zeros((B, 0, Rout - 1), np.int32),
-                    "nonbasis": np.zeros((B, 0, ldb - 1), np.int32)})
-        if log:
-            res["rc"] = np.zeros((B, 0, max(Pw, 1), 2), np.int32)
-        if ranging:
-            res.update({"rhs_lo": np.zeros((B, 0, Rout - 1)), "rhs_hi": np.zeros((B, 0, Rout - 1)),
-                        "cost_lo": np.zeros((B, 0, ldb - 1)), "cost_hi": np.zeros((B, 0, ldb - 1))})
-    return res
+
+    def make(stream, s0, c, d_final, d_dims, d_func, d_basis, d_nonbasis):
+        Q = B * c
+        d_tc = torch.empty((Q, Rout, ldb), dtype=torch.float64, device=dev)
+        d_dc = torch.empty((Q, 3), dtype=torch.int32, device=dev)
+        d_bc = torch.empty((Q, Rout), dtype=torch.int32, device=dev)
+        d_cs = d_cuts[:, s0:s0 + c].contiguous()             # named: alive until the launch
+        d_ns = d_nc[:, s0:s0 + c].contiguous()
+        _lib.check(L.smx_batch_cuts(
+            d_final.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, d_basis.data_ptr(),
+            d_nonbasis.data_ptr(), d_cs.data_ptr() if K else None, d_ns.data_ptr(), K, Rout,
+            d_tc.data_ptr(), d_dc.data_ptr(), d_bc.data_ptr(), stream.cuda_stream),
+            "smx_batch_cuts")
+        # every table's own start labels (group 1): its LP's column labels and function row
+        return (d_tc, d_dc, d_func.repeat_interleave(c, dim=0),
+                (d_bc, d_nonbasis.repeat_interleave(c, dim=0), 1))
+
+    return _warm_chain(L, dev, tabs, dims, which, P, S, make, Rout, warm, Pw, ranging, log)
 
 
 def _enlarged(cons, func, rows):
     """The ORIGINAL problem with a cut set's rows appended."""
     return [list(r) for r in cons] + [[float(v) for v in r] for r in rows], list(func)
-
-
-def _fallback_cuts(cons, func, sets, max_pivots, warm_pivots):
-    try:
-        sm = SimplexMethod(cons, func)
-        sm.solve(record_history=False, max_pivots=max_pivots)
-        base = sm.solution()
-        out = []
-        for rows in sets:
-            ext = sm.add_constraints(rows)
-            ext.solve(record_history=False, max_pivots=warm_pivots)
-            out.append(Scenario(ext.solution(), ext.status, True))
-        return base, out
-    except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
-        return exc, [Scenario(exc, "exception", True) for _ in sets]
 
 
 def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
@@ -1050,24 +990,20 @@ def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
     ``warm=False``."""
     problems = list(problems)
     cuts = [[[list(r) for r in rows] for rows in sets] for sets in cuts]
-    if kernel not in KERNELS:
-        raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+    _kernel_name(kernel)                                     # refused before the cuts are
     if len(cuts) != len(problems):
         raise ValueError("cuts must hold one list of cut sets per problem")
     for (c, _), sets in zip(problems, cuts):
         if any(len(r) != len(c[0]) for rows in sets for r in rows):
             raise ValueError("a cut must have the length of its problem's constraints")
-    if not torch.cuda.is_available():
-        raise RuntimeError("simplex_mi355x needs an MI355X (HIP device); there is no CPU path")
     P = int(max_pivots)
     Pw = P if warm_pivots is None else int(warm_pivots)
     results = [None] * len(problems)
-    routes = _routes(problems, kernel)
-    for k, (c, f) in enumerate(problems):
-        if routes[k] == "single":
-            results[k] = _fallback_cuts(c, f, cuts[k], P, Pw)
-    for which, idx in _launches(problems, routes, max_pivots, False):
-        tabs, dims = pack([problems[k] for k in idx])
+
+    def single(k, c, f):
+        results[k] = _fallback_warm(c, f, cuts[k], P, Pw, SimplexMethod.add_constraints)
+
+    def launch(which, idx, tabs, dims):
         _, Rmax, ldb = tabs.shape
         S = max(len(cuts[k]) for k in idx)
         K = max((len(rows) for k in idx for rows in cuts[k]), default=0)
@@ -1075,8 +1011,8 @@ def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
             warm_kernel(which, Rmax + K, ldb)
         except ValueError:
             for k in idx:
-                results[k] = _fallback_cuts(*problems[k], cuts[k], P, Pw)
-            continue
+                single(k, *problems[k])
+            return
         g = np.zeros((len(idx), S, K, ldb), dtype=np.float64)
         nc = np.zeros((len(idx), S), dtype=np.int32)
         for q, k in enumerate(idx):
@@ -1086,40 +1022,15 @@ def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
                 if rows:
                     g[q, s, :len(rows), :m + 1] = np.asarray(rows, dtype=np.float64)
         out = solve_batch_cuts_arrays(tabs, dims, g, nc, P, Pw, device, kernel=which)
-        base = out["base"]
         for q, k in enumerate(idx):
-            n, m = int(dims[q, 0]), int(dims[q, 1])
-            sol = Solution(base["x"][q, :m].copy(), base["duals"][q, :n].copy(),
-                           float(base["objective"][q]), base["basis"][q, :n].copy(),
-                           base["nonbasis"][q, :m].copy(), int(base["npivots"][q]))
-            answers = []
-            for s, rows in enumerate(cuts[k]):
-                np_, n2 = int(out["npivots"][q, s]), n + len(rows)
-                answers.append(Scenario(
-                    Solution(out["x"][q, s, :m].copy(), out["duals"][q, s, :n2].copy(),
-                             float(out["objective"][q, s]), out["basis"][q, s, :n2].copy(),
-                             out["nonbasis"][q, s, :m].copy(), np_),
-                    _status_name(int(out["status"][q, s]), np_, Pw), True))
-            results[k] = (sol, answers)
+            results[k] = _warm_answers(out, q, int(dims[q, 0]), int(dims[q, 1]),
+                                       [len(rows) for rows in cuts[k]], Pw)
+
+    _drive(problems, kernel, max_pivots, False, single, launch)
     if cold_fallback:
-        todo = [(k, s) for k, (_, answers) in enumerate(results) for s, sc in enumerate(answers)
-                if sc.status not in ("optimum", "exception")]
-        if todo:
-            cold = [_enlarged(*problems[k], cuts[k][s]) for k, s in todo]
-            sols, sts = solve_batch_solutions(cold, max_pivots, device, kernel)
-            for (k, s), sol, st in zip(todo, sols, sts):
-                results[k][1][s] = Scenario(sol, st, False)
+        _cold_tail(results, lambda k, s: _enlarged(*problems[k], cuts[k][s]), max_pivots, device,
+                   kernel)
     return results
-
-
-def _status_name(status, np_, P):
-    if status == _lib.OPTIMUM:
-        return "optimum"
-    if status in MESSAGES:
-        return "error"
-    if status == _lib.PIVOT and np_ >= P:
-        return "cap"
-    raise RuntimeError(f"unexpected batch status {status}")
 
 
 def _table(T, n, flen, m):
@@ -1162,11 +1073,7 @@ def _assemble(problem, dims, final, rc, xv, snaps, status, np_, P):
     if tables is None:  # like SimplexMethod.solve(record_history=False): initial + final
         res.append(Info.owning(row, col, _table(final, n, flen, m), None, None, x1, x2,
                                f0 * x1 + f1 * x2))
-    if status == _lib.OPTIMUM:
-        return res, "optimum"
-    if status in MESSAGES:
+    name = _status_name(status, np_, P)
+    if name == "error":
         res.append(Error(MESSAGES[status]))
-        return res, "error"
-    if status == _lib.PIVOT and np_ >= P:
-        return res, "cap"
-    raise RuntimeError(f"unexpected batch status {status}")
+    return res, name

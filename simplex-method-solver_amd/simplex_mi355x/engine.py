@@ -438,14 +438,57 @@ class SimplexMethod:
         x2 = vals[x2_i] if x2_i != self.invalid_index else 0
         return x1, x2
 
+    def _label_codes(self):
+        """``column`` / ``row`` as the int32 codes (basis [n], nonbasis [m]) of ``Solution``."""
+        m = self.m
+        return (np.array([_label_code(s, m) for s in self.column[:self.n]], dtype=np.int32),
+                np.array([_label_code(s, m) for s in self.row[:m]], dtype=np.int32))
+
+    def _dense_table(self):
+        """The current table as a dense float64 (n + 1) x (m + 1) array: the backend's
+        ``download()``, or before the first pivot the caller's own lists, where a short f-row
+        reads as +0.0."""
+        n, m = self.n, self.m
+        if not self._pristine:
+            return np.ascontiguousarray(self._dev.download()[:n + 1, :m + 1], dtype=np.float64)
+        T = np.zeros((n + 1, m + 1), dtype=np.float64)
+        T[:n] = self._initial[:n]
+        frow = self._initial[n][:m + 1]
+        T[n, :len(frow)] = frow
+        return T
+
+    def _successor(self, table, n, function, row, column, invalid_index):
+        """A new object on this one's backend around ``table`` ((n + 1) x (m + 1), already under
+        the labels ``row`` / ``column``): past its first pivot, with an empty pivot log."""
+        new = type(self).__new__(type(self))
+        new.n, new.m, new.flen = n, self.m, self.flen
+        new.invalid_index = invalid_index
+        new.function = function
+        new.row, new.column = row, column
+        new._initial = None
+        old = self._dev
+        if self.backend == "host":
+            new._dev = type(old)(table, n, self.m, self.flen)
+        elif self.backend == "sharded":
+            new._dev = type(old)(table, n, self.m, self.flen, old.devices, pivots=old.P,
+                                 exchange=old.exchange)
+        else:
+            new._dev = type(old)(table, n, self.m, self.flen, device=old.device)
+        new._pristine = False
+        new._int0 = new._int_hist = None
+        new.pivot_log = []
+        new.status = "ready"
+        new.cycle = None
+        new._tracker = None
+        return new
+
     def solution(self) -> Solution:
         """The current table's whole answer: ``find_optimum`` for every variable, the f-row
         entries under the slack labels and the objective on the ORIGINAL function, with the
         labels as int32 codes (``Solution``).  Values are read whatever ``status`` says; on the
         caller's own table (before the first pivot) every x and dual is +0.0."""
         n, m = self.n, self.m
-        basis = np.array([_label_code(s, m) for s in self.column[:n]], dtype=np.int32)
-        nonbasis = np.array([_label_code(s, m) for s in self.row[:m]], dtype=np.int32)
+        basis, nonbasis = self._label_codes()
         rows = [i for i in range(n) if basis[i] < m]
         cols = [j for j in range(m) if nonbasis[j] >= m]
         if self._pristine:        # the caller's own lists (labels may stand from an earlier run)
@@ -471,15 +514,8 @@ class SimplexMethod:
         before the first pivot), the rules from ``smx_host_ranging`` -- on every backend.  Values
         are formed whatever ``status`` says; they mean something at an optimum."""
         n, m = self.n, self.m
-        basis = np.array([_label_code(s, m) for s in self.column[:n]], dtype=np.int32)
-        nonbasis = np.array([_label_code(s, m) for s in self.row[:m]], dtype=np.int32)
-        if self._pristine:        # the caller's own lists; a short f-row reads as +0.0
-            T = np.zeros((n + 1, m + 1), dtype=np.float64)
-            T[:n] = self._initial[:n]
-            frow = self._initial[n][:m + 1]
-            T[n, :len(frow)] = frow
-        else:
-            T = np.ascontiguousarray(self._dev.download()[:n + 1, :m + 1], dtype=np.float64)
+        basis, nonbasis = self._label_codes()
+        T = self._dense_table()
         out = [np.empty(k, dtype=np.float64) for k in (n, n, m, m)]
         err = _lib.load().smx_host_ranging(T.ctypes.data, T.shape[1], n, m, basis.ctypes.data,
                                            nonbasis.ctypes.data, *(a.ctypes.data for a in out))
@@ -500,21 +536,14 @@ class SimplexMethod:
         from there.  Such a warm run need not terminate (the selection rule is no dual simplex):
         cap it with ``max_pivots`` and read ``status``."""
         n, m = self.n, self.m
-        basis = np.array([_label_code(s, m) for s in self.column[:n]], dtype=np.int32)
-        nonbasis = np.array([_label_code(s, m) for s in self.row[:m]], dtype=np.int32)
+        basis, nonbasis = self._label_codes()
         dr = np.zeros(n, dtype=np.float64)
         dc = np.zeros(m, dtype=np.float64)
         if drhs is not None:
             dr[:] = np.asarray(drhs, dtype=np.float64).reshape(n)
         if dcost is not None:
             dc[:] = np.asarray(dcost, dtype=np.float64).reshape(m)
-        if self._pristine:        # the caller's own lists; a short f-row reads as +0.0
-            T = np.zeros((n + 1, m + 1), dtype=np.float64)
-            T[:n] = self._initial[:n]
-            frow = self._initial[n][:m + 1]
-            T[n, :len(frow)] = frow
-        else:
-            T = np.ascontiguousarray(self._dev.download()[:n + 1, :m + 1], dtype=np.float64)
+        T = self._dense_table()
         func = np.zeros(m, dtype=np.float64)
         k = min(len(self.function), m)
         func[:k] = np.asarray(self.function[:k], dtype=np.float64)
@@ -526,29 +555,8 @@ class SimplexMethod:
             func_s.ctypes.data)
         if err:
             raise RuntimeError(f"smx_host_scenario refused n={n}, m={m} ({err})")
-        cls = type(self)
-        new = cls.__new__(cls)
-        new.n, new.m, new.flen = n, m, self.flen
-        new.invalid_index = self.invalid_index
-        fs = func_s.tolist()
-        new.function = fs + [float(v) for v in self.function[m:]]
-        new.row, new.column = list(self.row), list(self.column)
-        new._initial = None
-        old = self._dev
-        if self.backend == "host":
-            new._dev = type(old)(S, n, m, self.flen)
-        elif self.backend == "sharded":
-            new._dev = type(old)(S, n, m, self.flen, old.devices, pivots=old.P,
-                                 exchange=old.exchange)
-        else:
-            new._dev = type(old)(S, n, m, self.flen, device=old.device)
-        new._pristine = False
-        new._int0 = new._int_hist = None
-        new.pivot_log = []
-        new.status = "ready"
-        new.cycle = None
-        new._tracker = None
-        return new
+        return self._successor(S, n, func_s.tolist() + [float(v) for v in self.function[m:]],
+                               list(self.row), list(self.column), self.invalid_index)
 
     def add_constraints(self, rows) -> "SimplexMethod":
         """A new ``SimplexMethod`` on the extended table of the current one: every row of
@@ -568,15 +576,8 @@ class SimplexMethod:
             raise ValueError(f"a new constraint must hold {m} coefficients and a constant")
         K = len(rows)
         G = np.ascontiguousarray(rows, dtype=np.float64).reshape(K, m + 1)
-        basis = np.array([_label_code(s, m) for s in self.column[:n]], dtype=np.int32)
-        nonbasis = np.array([_label_code(s, m) for s in self.row[:m]], dtype=np.int32)
-        if self._pristine:        # the caller's own lists; a short f-row reads as +0.0
-            T = np.zeros((n + 1, m + 1), dtype=np.float64)
-            T[:n] = self._initial[:n]
-            frow = self._initial[n][:m + 1]
-            T[n, :len(frow)] = frow
-        else:
-            T = np.ascontiguousarray(self._dev.download()[:n + 1, :m + 1], dtype=np.float64)
+        basis, nonbasis = self._label_codes()
+        T = self._dense_table()
         E = np.empty((n + K + 1, m + 1), dtype=np.float64)
         basis_out = np.empty(n + K, dtype=np.int32)
         err = _lib.load().smx_host_cuts(
@@ -584,30 +585,10 @@ class SimplexMethod:
             G.ctypes.data if K else None, K, E.ctypes.data, E.shape[1], basis_out.ctypes.data)
         if err:
             raise RuntimeError(f"smx_host_cuts refused n={n}, m={m}, K={K} ({err})")
-        cls = type(self)
-        new = cls.__new__(cls)
-        new.n, new.m, new.flen = n + K, m, self.flen
-        new.invalid_index = 1 + max(n + K, m)
-        new.function = list(self.function)
-        new.row = list(self.row)
-        new.column = (list(self.column[:n]) + ['y' + str(n + c + 1) for c in range(K)]
-                      + list(self.column[n:]))
-        new._initial = None
-        old = self._dev
-        if self.backend == "host":
-            new._dev = type(old)(E, n + K, m, self.flen)
-        elif self.backend == "sharded":
-            new._dev = type(old)(E, n + K, m, self.flen, old.devices, pivots=old.P,
-                                 exchange=old.exchange)
-        else:
-            new._dev = type(old)(E, n + K, m, self.flen, device=old.device)
-        new._pristine = False
-        new._int0 = new._int_hist = None
-        new.pivot_log = []
-        new.status = "ready"
-        new.cycle = None
-        new._tracker = None
-        return new
+        column = (list(self.column[:n]) + ['y' + str(n + c + 1) for c in range(K)]
+                  + list(self.column[n:]))
+        return self._successor(E, n + K, list(self.function), list(self.row), column,
+                               1 + max(n + K, m))
 
     # ---------------------------------------------------------------- the hot path -------
     def pick_element(self) -> (bool, int, int, float):

@@ -350,6 +350,23 @@ def test_slices_of_cut_sets_give_the_same_answer(monkeypatch):
                 else np.array_equal(whole[key], sliced[key]), key
 
 
+def test_slices_with_ranges_and_the_warm_log_equal_the_whole_call(monkeypatch):
+    """The same budget with ``ranging`` and ``log`` named: the ranges, the warm pivot logs and
+    the base answers of the sliced call are the unsliced call's, key by key and bit by bit."""
+    from simplex_mi355x import batch
+    whole, _ = _chain(WAVE_MIX, 64, "wave", 5, 2, viol=0.2, ranging=True)
+    monkeypatch.setattr(batch, "GM_TABLE_BUDGET", 2 * 4 * 66 * 64 * 8)
+    sliced, _ = _chain(WAVE_MIX, 64, "wave", 5, 2, viol=0.2, ranging=True)
+    assert list(whole) == list(sliced) and list(whole["base"]) == list(sliced["base"])
+    assert {"rc", "rhs_lo", "rhs_hi", "cost_lo", "cost_hi"} <= set(whole)
+    assert whole["rc"].shape == (4, 5, 64, 2) and whole["rhs_lo"].shape == (4, 5, 62)
+    for a, b in ((whole, sliced), (whole["base"], sliced["base"])):
+        for key in a:
+            if key != "base":
+                assert a[key].dtype == b[key].dtype and a[key].shape == b[key].shape, key
+                assert a[key].tobytes() == b[key].tobytes(), key
+
+
 # ----------------------------------------------------------------------------------------------
 # tier crossings
 def _tiers_of(monkeypatch):
