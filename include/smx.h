@@ -597,8 +597,12 @@ int smx_tune_block_planner(int32_t planner, int32_t nwin);
  * 5 LDS, 6 LDS in work items (every workgroup's rows in K segments, each at another column chunk:
  * SMX_SWEEP_ITEMS=K, default 16), 7 LDS in row pairs (a lane keeps two rows of its two columns, so
  * each LDS read of a pivot's slice feeds four chains; the rows' multipliers in phases of 12
- * pivots; automatic from 20 pivots per sweep on tables with 64 to 2,047 rows per sweep wave, e.g.
- * 8192^2 and 16384^2: DESIGN 21); any other value keeps the setting.  Returns the previous one.
+ * pivots: DESIGN 21), 8 LDS in row quads (four rows per lane, eight chains per LDS read of a
+ * pivot's slice; the four rows' multipliers and the pivots' e and y as scalar operands in phases
+ * of 6 pivots; from 13 pivots per sweep on, below that it runs 5; automatic at 20, 22, 23 and 24
+ * pivots per sweep on tables with 64 to 2,047 rows per sweep wave, e.g. 8192^2 and 16384^2, where
+ * 21 pivots keep 7: DESIGN 23); any
+ * other value keeps the setting.  Returns the previous one.
  * Same bits either way. */
 int smx_tune_block_form(int32_t form);
 int64_t smx_block_bytes(const smx_shape* shape, int32_t* pivots_inout);

@@ -530,14 +530,23 @@ using BshPackFn = void (*)(const double*, int64_t, int, int, int, int, int, cons
                            const BlkHdr*, const smx_part*, int, const double*, const double*,
                            double*);
 
-// Sweep kernels by pivot count (1..kBlkMax) and layout (FORM 4 / 5 / 6 / 7, blk_sweep_body_flag)
+// Sweep kernels by pivot count (1..kBlkMax) and layout (FORM 4 / 5 / 6 / 7 / 8,
+// blk_sweep_body_flag).  FORM 8 exists from kQuadMinP pivots on: below, it is FORM 5's kernel.
 template <int FORM, int... Is>
 BlkSweepFn blk_sweep_pick(int P, std::integer_sequence<int, Is...>) {
     static const BlkSweepFn t[] = {k_blk_sweep<Is + 1, FORM>...};
     return t[P - 1];
 }
+template <int... Is>
+BlkSweepFn blk_sweep_pick_quad(int P, std::integer_sequence<int, Is...>) {
+    static const BlkSweepFn t[] = {k_blk_sweep<Is + kQuadMinP, 8>...};
+    return t[P - kQuadMinP];
+}
 BlkSweepFn blk_sweep_fn(int P, int form) {
     using All = std::make_integer_sequence<int, kBlkMax>;
+    if (form == 8 && P >= kQuadMinP)
+        return blk_sweep_pick_quad(P, std::make_integer_sequence<int, kBlkMax - kQuadMinP + 1>{});
+    if (form == 8) form = 5;
     return form == 7 ? blk_sweep_pick<7>(P, All{})
            : form == 6 ? blk_sweep_pick<6>(P, All{})
                      : form == 5 ? blk_sweep_pick<5>(P, All{}) : blk_sweep_pick<4>(P, All{});
@@ -701,7 +710,7 @@ int launch_blk_publish(bool sh, const smx_shape& s, int parity, int bn, smx_ctl*
 
 // Sweep layout (smx_tune_block_form): 0 automatic -- the register layout (4) up to kSweepRegMaxP
 // pivots, the LDS layout (5) beyond and wherever the register layout's grid cannot give every
-// wave one chunk; 4 / 5 / 6 / 7 forced (tests, A/B timing).
+// wave one chunk; 4 / 5 / 6 / 7 / 8 forced (tests, A/B timing; 8 below kQuadMinP pivots runs 5).
 int g_block_form = 0;
 constexpr int kSweepRegMaxP = 12;
 constexpr int64_t kSweepItemRows = 2048;   // rows per wave from which FORM 6 is automatic
@@ -712,6 +721,14 @@ constexpr int64_t kSweepItemRows = 2048;   // rows per wave from which FORM 6 is
 // per wave) 363 -> 351 at 20 and 428 -> 419 at 24 (ranges 425-434 and 410-426: they touch).  At
 // 4096^2 (16 rows per wave) 131 -> 128 at 24 and 94 -> 93 at 16: inside the spread, FORM 5 stays;
 // 13-19 pivots were not measured.
+// FORM 8 (row quads) took FORM 7's place there: parent (FORM 7) and new build interleaved on one
+// box, mean sweep in us, 6 runs each, every new run below every parent run in each cell
+// (profiles/quads/ab_sweeps.jsonl): 16384^2 1565 -> 1485 / 1700 -> 1585 / 1752 -> 1669
+// / 1818 -> 1702 at 20 / 22 / 23 / 24 pivots, 8192^2 342 -> 335 / 376 -> 365 / 393 -> 383 / 404 ->
+// 392.  At 21 pivots 16384^2 gave 1624 -> 1565 with the ranges touching (1601-1647, 1522-1603;
+// 8192^2 362 -> 355, clear), so 21 keeps FORM 7.  Below 20 pivots and below 64 rows per wave
+// nothing was measured and the launch is what it was.
+constexpr int kSweepQuadSkipP = 21;
 constexpr int kSweepPairMinP = 20;
 constexpr int64_t kSweepPairRows = 64;
 
@@ -735,7 +752,7 @@ int launch_block_sweep(bool sh, double* tin, double* tother, const smx_shape& s,
                        int in_idx = 0, int ipx_part = 0, smx_ctl* pub_ctl = nullptr,
                        int pub_bn = 0, int pub_parity = 0) {
     const int nchunks = (s.m + 1 + 2 * kWave - 1) / (2 * kWave);
-    int form = g_block_form >= 4 && g_block_form <= 7 ? g_block_form
+    int form = g_block_form >= 4 && g_block_form <= 8 ? g_block_form
                                                       : (P > kSweepRegMaxP ? 5 : 4);
     int grid = 0;
     if (form == 4) {
@@ -753,7 +770,7 @@ int launch_block_sweep(bool sh, double* tin, double* tother, const smx_shape& s,
         const int64_t per = sweep_grid_lds(s, g_blocks_per_cu > 0 ? g_blocks_per_cu : 8) / nchunks;
         if ((int64_t)(s.rows + 1) >= per * kUpdWaves * kSweepItemRows) form = 6;
         else if (P >= kSweepPairMinP && (int64_t)(s.rows + 1) >= per * kUpdWaves * kSweepPairRows)
-            form = 7;
+            form = P == kSweepQuadSkipP ? 7 : 8;
     }
     BlkSweepFn fn = blk_sweep_fn(P, form);
     if (form >= 5)   // a grid of 8 workgroups per CU.  At P = 20 only 7 are resident (P KiB of
@@ -763,6 +780,8 @@ int launch_block_sweep(bool sh, double* tin, double* tother, const smx_shape& s,
                      // at 8 / 7 / 6 (profiles/r05a/).  FORM 7 (60 VGPRs at P = 24, 6 resident):
                      // mean sweep 1865 / 1876 / 1906 us at 24 pivots and 1580 / 1584 / 1608 at 20
                      // with the grid sized for 8 / 7 / 6 (profiles/r07/ab2_sweeps.jsonl): 8 stays.
+                     // FORM 8 (75 VGPRs at P = 24, 6 resident): 1702 / 1714 / 1731 us at 24 and
+                     // 1485 / 1487 / 1491 at 20 (profiles/quads/ab_sweeps.jsonl): 8 stays.
                      // smx_tune_set(-2, bpc) overrides it.
         grid = sweep_grid_lds(s, g_blocks_per_cu > 0 ? g_blocks_per_cu : 8);
     BlkHdr* hs = reinterpret_cast<BlkHdr*>(blk);
@@ -1852,7 +1871,7 @@ int smx_diag_path_counts(int64_t* out, int32_t count, int32_t clear) {
 
 int smx_tune_block_form(int32_t form) {
     const int prev = g_block_form;
-    if (form == 0 || (form >= 4 && form <= 7)) g_block_form = form;
+    if (form == 0 || (form >= 4 && form <= 8)) g_block_form = form;
     return prev;
 }
 

@@ -10,11 +10,11 @@
 //   the path counters        diagnostic build only
 //   BlkChunk                 the chunk a wave is sweeping and which paths it allows
 //   BlkRegOps / BlkLdsOps    where a pivot's row slice and (e, y) come from: registers (FORM 4)
-//                            or LDS (FORM 5 / 6 / 7), with the fast and zero-safe row paths
-//   blk_row_pairs            FORM 7's prefetch loop over row pairs
+//                            or LDS (FORM 5 / 6 / 7 / 8), with the fast and zero-safe row paths
+//   blk_row_pairs / _quads   FORM 7's and 8's prefetch loops over row pairs and row quads
 //   blk_geom_wave / _wg      a wave's chunk, first row and row stride, per layout
 //   blk_sweep_body_flag      the sweep of one block: staging, chunk flags, a row (rowf), a row
-//                            pair (pairf), the row loops
+//                            pair (pairf), a row quad (quadf), the row loops
 //   blk_fixcols, blk_out, k_blk_sweep, k_blk_sweep_rest
 // What is written in place where it is used, and not as a function of its own, is so because the
 // function form changed the kernels' instructions.
@@ -109,7 +109,7 @@ __device__ __forceinline__ dbl2 blk_exact_h(dbl2 v, int row, int j, const BlkHdr
 // domain take the zero-safe path, then the window-tracked path (a pivot column's zero numerator
 // fails its vote), then the exact path, which applies every rule itself.
 //
-// The layouts (FORM; 6 and 7 are described at g_sweep_items and kPairPhase):
+// The layouts (FORM; 6, 7 and 8 are described at g_sweep_items, kPairPhase and kQuadPhase):
 //  4  wave-chunk: every wave keeps one 128-column chunk (w % nchunks) for the whole pass, its
 //     pivot-row slices in registers (2P doubles per lane) and e / y in scalar registers -- the
 //     fastest up to ~12 pivots (profiles/r03/, tools/sweep_lab2.hip V1);
@@ -196,6 +196,34 @@ __device__ __forceinline__ void blk_pair_step(dbl2& va, dbl2& vb, dbl2 p, dbl2 e
     const dbl2 nb = blk_num(vb, e, p, mb);
     va = blk_quot_fast(na, e, y);
     vb = blk_quot_fast(nb, e, y);
+}
+
+// FORM 8: the LDS layout in row quads.  FORM 7's grid, chunk ownership, staging and chunk flags; a
+// lane keeps FOUR rows of its two columns (rows i0, i0 + qs, i0 + 2 qs, i0 + 3 qs of its wave), so
+// each ds_read_b128 of a pivot's row slice feeds eight chains, and (e, y) are not read from LDS at
+// all: a wave-uniform pair returned into 4 VGPRs x 64 lanes was half of FORM 7's LDS reads.  The
+// pivots are taken in phases of kQuadPhase; where a phase begins, one scalar round trip loads the
+// four rows' multipliers of the phase (4 x 6 doubles, the 48 scalar registers of FORM 7's phase)
+// and the phase's e and y (24 more).  A quad is fast only when all four rows exist and are flagged
+// 1, the chunk is free and one vote over the eight inputs passes; any other quad, and a tail of
+// 1-3 rows, goes row by row through FORM 5's single-row code, unchanged.  Instantiated from
+// kQuadMinP pivots on (blk_sweep_fn).
+constexpr int kQuadPhase = 6;
+constexpr int kQuadMinP = 13;
+
+// One pivot of a row quad's fast path: eight chains, each the one-row fast path's six
+// instructions in its order, with e, y and the multipliers as scalar operands.
+__device__ __forceinline__ void blk_quad_step(dbl2& v0, dbl2& v1, dbl2& v2, dbl2& v3, dbl2 p,
+                                              double e, double y, double m0, double m1, double m2,
+                                              double m3) {
+    const dbl2 n0 = blk_num(v0, e, p, m0);
+    const dbl2 n1 = blk_num(v1, e, p, m1);
+    const dbl2 n2 = blk_num(v2, e, p, m2);
+    const dbl2 n3 = blk_num(v3, e, p, m3);
+    v0 = blk_quot_fast(n0, e, y);
+    v1 = blk_quot_fast(n1, e, y);
+    v2 = blk_quot_fast(n2, e, y);
+    v3 = blk_quot_fast(n3, e, y);
 }
 
 // The chunk a wave is sweeping: its place, and which paths its pivots and pivot-row values allow.
@@ -322,6 +350,38 @@ __device__ __forceinline__ void blk_row_pairs(LDC ldc, PAIRF pairf, int r0, int 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// Rows r0, r0 + qs, ... below hi four at a time (FORM 8; quadf(x0, x1, x2, x3, row, hi): the
+// sweep of rows row .. row + 3 qs).  Prefetch depth 1 over quads: before a quad's registers are
+// used, the ops issued after its four loads are the previous quad's four stores (fewer only for a
+// tail, and then no quad follows) and the other quad's four loads: vmcnt(8); vmcnt(4) first
+template <class LDC, class QUADF>
+__device__ __forceinline__ void blk_row_quads(LDC ldc, QUADF quadf, int r0, int qs, int hi) {
+    int i0 = r0;
+    dbl2 a0 = ldc(i0), a1 = ldc(i0 + qs), a2 = ldc(i0 + 2 * qs), a3 = ldc(i0 + 3 * qs);
+    dbl2 b0 = ldc(i0 + 4 * qs), b1 = ldc(i0 + 5 * qs), b2 = ldc(i0 + 6 * qs),
+         b3 = ldc(i0 + 7 * qs);
+    asm volatile("s_waitcnt vmcnt(4)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) :: "memory");
+    for (;;) {
+        quadf(a0, a1, a2, a3, i0, hi);
+        i0 += 4 * qs;
+        if (i0 >= hi) break;
+        a0 = ldc(i0 + 4 * qs);
+        a1 = ldc(i0 + 5 * qs);
+        a2 = ldc(i0 + 6 * qs);
+        a3 = ldc(i0 + 7 * qs);
+        asm volatile("s_waitcnt vmcnt(8)" : "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3) :: "memory");
+        quadf(b0, b1, b2, b3, i0, hi);
+        i0 += 4 * qs;
+        if (i0 >= hi) break;
+        b0 = ldc(i0 + 4 * qs);
+        b1 = ldc(i0 + 5 * qs);
+        b2 = ldc(i0 + 6 * qs);
+        b3 = ldc(i0 + 7 * qs);
+        asm volatile("s_waitcnt vmcnt(8)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) :: "memory");
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 // A wave's share of the table: its chunk, its first row and the stride to its next row.
 struct BlkGeom {
     int ch, base, qs;
@@ -349,6 +409,7 @@ __device__ __forceinline__ void blk_sweep_body_flag(const double* Tin, double* T
     constexpr bool LDS = FORM >= 5;
     constexpr bool ITEMS = FORM == 6;
     constexpr bool PAIRS = FORM == 7;
+    constexpr bool QUADS = FORM == 8;
     __shared__ dbl2 s_pr[LDS ? P : 1][kWave];
     __shared__ dbl2 s_ey[LDS ? P : 1];
     // the zero-extended path's scalars (M_q, |y_q|) and -sgn(e_{P-1}): blk_step_zneg
@@ -587,6 +648,86 @@ __device__ __forceinline__ void blk_sweep_body_flag(const double* Tin, double* T
             for (int s = 0; s < (two ? 2 : 1); ++s) rowf(s ? xb : xa, s ? ib : ia);
         }
     };
+    // FORM 8: rows ia, ia + qs, ia + 2 qs, ia + 3 qs together (x0..x3: their inputs; hi: the end of
+    // the wave's rows)
+    auto quadf = [&](dbl2 x0, dbl2 x1, dbl2 x2, dbl2 x3, int ia, int hi) {
+        constexpr int NPH = (P + kQuadPhase - 1) / kQuadPhase;
+        constexpr int P0 = P < kQuadPhase ? P : kQuadPhase;
+        // rows of the quad inside the wave's rows (1-3: a tail, row by row)
+        const int nr = ia + 3 * qs < hi ? 4 : ia + 2 * qs < hi ? 3 : ia + qs < hi ? 2 : 1;
+        const bool four = nr == 4;
+        const int i1 = four ? ia + qs : ia;   // (nothing read past the table's rows)
+        const int i2 = four ? ia + 2 * qs : ia;
+        const int i3 = four ? ia + 3 * qs : ia;
+        const double* m0 = mul + (int64_t)ia * kBlkMax;
+        const double* m1 = mul + (int64_t)i1 * kBlkMax;
+        const double* m2 = mul + (int64_t)i2 * kBlkMax;
+        const double* m3 = mul + (int64_t)i3 * kBlkMax;
+        int rf0 = rfl[ia], rf1 = rfl[i1], rf2 = rfl[i2], rf3 = rfl[i3];
+        asm volatile("" : "+s"(rf0));
+        asm volatile("" : "+s"(rf1));
+        asm volatile("" : "+s"(rf2));
+        asm volatile("" : "+s"(rf3));
+        auto hi2 = [](dbl2 x) {
+            return max((uint32_t)__double2hiint(x[0]) << 1, (uint32_t)__double2hiint(x[1]) << 1);
+        };
+        const uint32_t xt = max(max(hi2(x0), hi2(x1)), max(hi2(x2), hi2(x3)));
+        if (four && c.free && rf0 == 1 && rf1 == 1 && rf2 == 1 && rf3 == 1 &&
+            __all(xt < kBndXMax)) {
+            SMX_PC(kPcFast);   // four (row, chunk) units
+            SMX_PC(kPcFast);
+            SMX_PC(kPcFast);
+            SMX_PC(kPcFast);
+            dbl2 v0 = x0, v1 = x1, v2 = x2, v3 = x3;
+            double p0[P0], p1[P0], p2[P0], p3[P0], pe[P0], py[P0];
+#pragma unroll
+            for (int ph = 0; ph < NPH; ++ph) {
+                const int q0 = ph * kQuadPhase;
+                const int nq = P - q0 < kQuadPhase ? P - q0 : kQuadPhase;
+                // This phase's multipliers of the four rows and its pivots' e and y, one scalar
+                // round trip, waited for in place; the offset tied to the chains' values as in
+                // pairf (and for its reasons), so a phase's loads are issued after the phase before
+                int o = q0;
+                asm volatile("" : "+s"(o) : "v"(v0), "v"(v1), "v"(v2), "v"(v3));
+#pragma unroll
+                for (int q = 0; q < nq; ++q) {
+                    p0[q] = m0[o + q];
+                    p1[q] = m1[o + q];
+                    p2[q] = m2[o + q];
+                    p3[q] = m3[o + q];
+                    pe[q] = h->e[o + q];
+                    py[q] = h->y[o + q];
+                }
+#pragma unroll
+                for (int q = 0; q < nq; ++q) {
+                    asm volatile("" : "+s"(p0[q]));
+                    asm volatile("" : "+s"(p1[q]));
+                    asm volatile("" : "+s"(p2[q]));
+                    asm volatile("" : "+s"(p3[q]));
+                    asm volatile("" : "+s"(pe[q]));
+                    asm volatile("" : "+s"(py[q]));
+                }
+#pragma unroll
+                for (int q = 0; q < nq; ++q)
+                    blk_quad_step(v0, v1, v2, v3, s_pr[q0 + q][lane], pe[q], py[q], p0[q], p1[q],
+                                  p2[q], p3[q]);
+            }
+            // (pinned before the store's branch, as in pairf)
+            asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3));
+            if (c.j < C) {
+                double* o0 = Tout + (int64_t)ia * ld + c.j;
+                __builtin_nontemporal_store(v0, reinterpret_cast<dbl2*>(o0));
+                __builtin_nontemporal_store(v1, reinterpret_cast<dbl2*>(o0 + (int64_t)qs * ld));
+                __builtin_nontemporal_store(v2, reinterpret_cast<dbl2*>(o0 + 2 * (int64_t)qs * ld));
+                __builtin_nontemporal_store(v3, reinterpret_cast<dbl2*>(o0 + 3 * (int64_t)qs * ld));
+            }
+        } else {
+            // row by row (each loads its own flag and multipliers: not the bench's path)
+#pragma nounroll
+            for (int s = 0; s < nr; ++s)
+                rowf(s == 0 ? x0 : s == 1 ? x1 : s == 2 ? x2 : x3, ia + s * qs);
+        }
+    };
     if constexpr (!ITEMS) {
         if (base >= R) return;
     }
@@ -613,6 +754,10 @@ __device__ __forceinline__ void blk_sweep_body_flag(const double* Tin, double* T
         const int r0 = lo + base;
         if constexpr (PAIRS) {
             blk_row_pairs(ldc, pairf, r0, qs, hi);
+            continue;
+        }
+        if constexpr (QUADS) {
+            blk_row_quads(ldc, quadf, r0, qs, hi);
             continue;
         }
         dbl2 a = ldc(r0), b = ldc(r0 + qs);
@@ -697,7 +842,7 @@ __device__ __forceinline__ double* blk_out(double* b_in, double* b_other, int ip
 
 // The sweep of a block that applied all P of its pivots (h->peff == P; otherwise it does nothing
 // and k_blk_sweep_rest handles the block): one body per kernel, so the register allocation is
-// that body's alone.  FORM 4 / 5 / 6 / 7: blk_sweep_body_flag's layouts.  Output per blk_out.
+// that body's alone.  FORM 4 / 5 / 6 / 7 / 8: blk_sweep_body_flag's layouts.  Output per blk_out.
 template <int P, int FORM>
 __global__ __launch_bounds__(kUpdBlock) void k_blk_sweep(double* b_in, double* b_other, int64_t ld,
                                                          int R, int C,

@@ -341,8 +341,10 @@ def tune_block_planner(planner: int = -1, nwin: int = -1) -> int:
 def tune_block_form(form: int = -1) -> int:
     """smx_tune_block_form: 0 automatic, 4 pivot-row slices in registers, 5 in LDS, 6 in LDS by
     work items (rows in segments, each at another column chunk), 7 in LDS by row pairs (two rows
-    per lane share each pivot's LDS operands; multipliers in phases of 12 pivots); any other
-    value only queries; returns the previous setting."""
+    per lane share each pivot's LDS operands; multipliers in phases of 12 pivots), 8 in LDS by
+    row quads (four rows per lane share each pivot's row slice; the rows' multipliers and the
+    pivots' (e, y) as scalar operands in phases of 6 pivots; from 13 pivots per sweep on, form 5's
+    kernel below); any other value only queries; returns the previous setting."""
     return int(load().smx_tune_block_form(form))
 
 

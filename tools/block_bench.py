@@ -28,7 +28,8 @@ def main() -> None:
     ap.add_argument("--bpc", type=int, default=0, help="blocks per CU of the sweep (0: library)")
     ap.add_argument("--form", default="0",
                     help="smx_tune_block_form settings to compare, e.g. 5,7 (0 the library's "
-                         "policy, 4 registers, 5 LDS, 6 LDS work items, 7 LDS row pairs)")
+                         "policy, 4 registers, 5 LDS, 6 LDS work items, 7 LDS row pairs, 8 LDS row "
+                         "quads)")
     ap.add_argument("--planner", default="0",
                     help="smx_tune_block_planner settings to compare (0 the window planner, persistent where "
                          "eligible, 2 its launch form, 1 the "

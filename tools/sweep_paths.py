@@ -37,7 +37,7 @@ def main() -> None:
     ap.add_argument("--k", type=int, default=200)
     ap.add_argument("--idle", type=float, default=0.0)
     ap.add_argument("--bpc", type=int, default=0, help="sweep blocks per CU (0: library)")
-    ap.add_argument("--form", type=int, default=0, help="smx_tune_block_form (0: library; 4 / 5 / 6 / 7)")
+    ap.add_argument("--form", type=int, default=0, help="smx_tune_block_form (0: library; 4 / 5 / 6 / 7 / 8)")
     a = ap.parse_args()
     import ctypes
 

@@ -4,7 +4,7 @@
 
 Uploads the LP, runs `reps` timed block chains of k pivots (k = 0: --blocks blocks of that many pivots) from the
 same start (HIP events around every sweep) for every pivot count given, prints one JSON line per
-rep.  --form: smx_tune_block_form (0 the library's policy, 5 one row per lane, 7 row pairs).  Small and deterministic so every `--pmc` pass sees
+rep.  --form: smx_tune_block_form (0 the library's policy, 5 one row per lane, 7 row pairs, 8 row quads).  Small and deterministic so every `--pmc` pass sees
 the same dispatches (tools/pmc_sweep.sh).
 """
 from __future__ import annotations
@@ -24,7 +24,8 @@ def main() -> None:
     ap.add_argument("--pivots", default="8")
     ap.add_argument("--k", type=int, default=32)
     ap.add_argument("--reps", type=int, default=2)
-    ap.add_argument("--form", type=int, default=0)
+    ap.add_argument("--form", type=int, default=0,
+                    help="smx_tune_block_form (0 the library's policy; 4 / 5 / 6 / 7 / 8)")
     ap.add_argument("--blocks", type=int, default=1, help="with --k 0: blocks per chain")
     ap.add_argument("--bpc", type=int, default=0,
                     help="sweep workgroups per CU the grid is sized for (0: the library's 8)")
