@@ -62,7 +62,7 @@ typedef struct smx_ctl {
     double sel_e;       /* last selection: pivot element T[r][c]                              */
     int64_t npivots;    /* pivots applied since smx_reset(..., clear_count=1)                 */
     int32_t sel_owner;  /* sharded: rank whose candidate row is the pivot row                 */
-    int32_t nla;        /* sharded fused update: look-ahead workgroups done (0 between launches) */
+    int32_t nla;        /* unused; kept for layout */
     int64_t shard_off;  /* sharded: offset (doubles) of the pivot row in the receive buffer   */
     int32_t xpos[2][2]; /* [parity][x1, x2]: position code of labels 'x1', 'x2' (simplex.py:
                            58-59): p >= 0 row p (basic), -(j+1) column j, SMX_ABSENT none      */
@@ -123,18 +123,14 @@ int smx_set_xpos(smx_ctl* ctl, int32_t parity, int32_t x1code, int32_t x2code, v
 int smx_select(const double* T, const smx_shape* shape, int32_t parity, smx_ctl* ctl,
                smx_part* parts, void* stream);
 
-/* Fused chain (default for smx_run / smx_run_timed / smx_graph_*; `on`: 0 off, 1 on, 2 on plus
- * the overlapped form of smx_shard_run): ONE kernel per pivot --
- * the update of step k, whose first nparts workgroups also compute step k+1's select inputs
- * (first negative new "-b" row, entering column, ratio-test partials) from T_k with the update's
- * own arithmetic (bit-identical); a chain is primed by one small kernel and ends with a one-wave
+/* Fused chain (default for smx_run / smx_run_timed / smx_graph_* / smx_shard_run; `on`: 0 off,
+ * any value >= 1 on, -1 only queries; the setting is 0 or 1): ONE kernel per pivot -- the update
+ * of step k, whose first nparts workgroups also compute step k+1's select inputs (first negative
+ * new "-b" row, entering column, ratio-test partials) from T_k with the update's own arithmetic
+ * (bit-identical); a chain is primed by one small kernel and ends with a one-wave
  * publish of ctl->negb.  Records are double-buffered: `parts` must hold 2 * nparts of them.
  * smx_tune_fused(0) restores the select + update pair; returns the previous setting. */
 int smx_tune_fused(int32_t on);
-/* Smallest local tableau buffer (bytes) for which the sharded fused update packs the next step
- * itself (smx_shard_folds_pack; default INT64_MAX = never, it measured slower); -1 keeps it;
- * returns the previous value. */
-int64_t smx_tune_fold(int64_t min_bytes);
 
 /* pick_element, part 2: reduce the partials into ctl->sel_* (does not set term, logs nothing). */
 int smx_finalize(const double* T, const smx_shape* shape, int32_t parity, smx_ctl* ctl,
@@ -440,11 +436,10 @@ int smx_shard_finish(const double* Tin, double* Tout, const double* recv, int32_
 /* The same pivot with the fused look-ahead (no select kernel): smx_shard_fused_begin packs the
  * header and candidate rows from this step's look-ahead records (parts slot `parity`, written by
  * smx_shard_fused_prime for the first step of a sequence, by the previous fused finish after
- * that); smx_shard_fused_finish merges, updates and writes the next step's records -- and, when
- * `send` is not NULL and smx_shard_folds_pack(shape) (off by default, see smx_tune_fold),
- * already packs the next step into it: then skip the next begin.  Before switching
- * back to the unfused calls, smx_fused_publish(next parity) restores ctl->negb. */
-int smx_shard_folds_pack(const smx_shape* shape);
+ * that); smx_shard_fused_finish merges, updates and writes the next step's records.  Its `send`
+ * is ignored (kept so the call's signature stays as it was); every step begins with its own
+ * smx_shard_fused_begin.  Before switching back to the unfused calls, smx_fused_publish(next
+ * parity) restores ctl->negb. */
 int smx_shard_fused_prime(const double* T, const smx_shape* shape, int32_t parity, smx_ctl* ctl,
                           smx_part* parts, void* stream);
 int smx_shard_fused_begin(const double* T, const smx_shape* shape, int32_t parity,
@@ -461,27 +456,13 @@ int smx_fused_publish(const smx_shape* shape, int32_t parity, smx_ctl* ctl,
 int smx_copy_probe(const double* src, double* dst, int64_t ndoubles, int32_t variant,
                    void* stream);
 
-/* The two halves of a step of the overlapped chain (smx_shard_run's default form), for callers
- * that drive the exchange themselves: after step k's all-gather into `recv`,
- * smx_shard_ahead computes step k+1's records (parts slot parity^1) and packs step k+1's header
- * and candidate rows into `send` from T_k (it may run concurrently with the sweep, on another
- * stream); smx_shard_sweep is step k's update.  Start a sequence with smx_shard_fused_prime +
- * smx_shard_fused_begin. */
-int smx_shard_ahead(const double* T, const smx_shape* shape, int32_t parity, const double* recv,
-                    int32_t nranks, smx_ctl* ctl, smx_part* parts, double* send, void* stream);
-int smx_shard_sweep(const double* Tin, double* Tout, const double* recv, int32_t nranks,
-                    const smx_shape* shape, int32_t parity, smx_ctl* ctl, int32_t* log,
-                    int64_t log_cap, void* stream);
-
 /* Native RCCL driver (one communicator per rank; the unique id is created on rank 0 and
  * shipped to the others by any bootstrap, e.g. torch.distributed.broadcast_object_list).
- * smx_shard_run = k x {select, pack, ncclAllGather on `stream`, update}; with smx_tune_fused(1)
- * (the default) prime + pack + k x {ncclAllGather, fused update that also packs the next step}
- * + publish; with
- * smx_tune_fused(2) the overlapped form: the update sweeps on `stream` while an internal exchange
- * stream computes the next step's look-ahead records, header and candidate rows from T_k and
- * gathers them (two events per step).  No host synchronisation.  `recv` must hold
- * 2 * nranks * (SMX_SHARD_HDR + 2 * ld) doubles (the second half is used by the overlapped form).  RCCL failures are returned as -1000 - ncclResult_t. */
+ * smx_shard_run has two forms: with smx_tune_fused(0), k x {select, pack, ncclAllGather on
+ * `stream`, update}; with smx_tune_fused(1) (the default), prime + k x {pack, ncclAllGather,
+ * fused update that also writes the next step's records} + publish.  No host synchronisation.
+ * `recv` must hold nranks * (SMX_SHARD_HDR + 2 * ld) doubles.  RCCL failures are returned as
+ * -1000 - ncclResult_t. */
 int smx_comm_unique_id(void* id_out /* 128 bytes */);
 int smx_comm_init(void** comm_out, int32_t nranks, const void* id, int32_t rank);
 int smx_comm_destroy(void* comm);

@@ -164,21 +164,12 @@ int g_variant = -1;       // smx_tune_set overrides
 constexpr int kLargeVariant = 1, kSmallVariant = 0;
 constexpr int64_t kCacheTable = 16ll << 20;
 constexpr int64_t kLaSweepTable = 256ll << 20;
-// Sharded fused update: its last look-ahead workgroup can pack the next step itself (pivot =
-// update + all-gather).  Off by default: measured at world size 1 (tools/fold_ab.py,
-// profiles/r01_fold_ab.jsonl) it adds ~40 us per pivot at the 4- and 8-GPU per-rank shapes
-// (4097 / 2049 x 16384: that workgroup's share of the sweep starts late and per-wave throughput
-// is latency-bound) and gains nothing at 16384^2; the separate k_pack<true> wins everywhere.
-int64_t g_fold_min_bytes = INT64_MAX;   // smx_tune_fold
-inline bool folds_pack(const smx_shape& s) {
-    return (int64_t)(s.rows + 1) * s.ld * 8 >= g_fold_min_bytes;
-}
 int g_blocks_per_cu = 0;  // 0: kDefaultBpc, capped by the occupancy API (see blocks_per_cu)
 constexpr int kDefaultBpc = 5;
 
 using UpdFn = void (*)(const double*, double*, int64_t, int, int, int, int, int, int, int,
                        smx_ctl*, const smx_part*, int, int32_t*, double*, int64_t, const double*,
-                       int, int, double*);
+                       int, int);
 
 template <int MODE>
 UpdFn upd_fn(int v) {
@@ -290,8 +281,7 @@ int update_grid(const smx_shape& s, const void* fn, int reserved, int bpc = 0) {
 template <int MODE>
 int launch_update_mode(const double* Tin, double* Tout, const smx_shape& s, int parity,
                        smx_ctl* ctl, const smx_part* parts, int32_t* log, double* xhist,
-                       int64_t log_cap, const double* recv, int fr, int fc, hipStream_t st,
-                       int reserve = 0, double* send = nullptr) {
+                       int64_t log_cap, const double* recv, int fr, int fc, hipStream_t st) {
     const int v = variant_for(s);
     UpdFn fn = upd_fn<MODE>(v);
     // kFused: the first nparts workgroups compute the look-ahead records; within the Infinity
@@ -299,15 +289,13 @@ int launch_update_mode(const double* Tin, double* Tout, const smx_shape& s, int 
     // they sweep too (profiles/r01_sweep_small.jsonl)
     constexpr bool LA = MODE == kFused || MODE == kShardFused;
     const bool la_sweep = LA && (int64_t)(s.rows + 1) * s.ld * 8 > kLaSweepTable;
-    // reserve: resident slots left free for kernels of another stream (overlapped shard chain)
-    int grid = update_grid(s, (const void*)fn, (LA && !la_sweep ? s.nparts : 0) + reserve) -
-               reserve;
+    int grid = update_grid(s, (const void*)fn, LA && !la_sweep ? s.nparts : 0);
     if (grid < s.nparts) grid = s.nparts;
     if (grid < 1) grid = 1;
     if (LA) fr = la_sweep ? 1 : 0;   // kShardFused: fc = rank count (caller)
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kUpdBlock), 0, st, Tin,
                        Tout, s.ld, s.rows, s.n, s.m, s.flen, fscan_of(s), s.row0, parity, ctl,
-                       parts, s.nparts, log, xhist, log_cap, recv, fr, fc, send);
+                       parts, s.nparts, log, xhist, log_cap, recv, fr, fc);
     return (int)hipGetLastError();
 }
 
@@ -318,10 +306,7 @@ int launch_update(const double* Tin, double* Tout, const smx_shape& s, int parit
                                        nullptr, 0, 0, st);
 }
 
-// Chains (smx_tune_fused): 0 select + update; 1 one fused kernel per pivot (default); 2 as 1, and
-// the sharded chain overlaps the next step's look-ahead + all-gather with the sweep on a second
-// stream -- correct, but slower on this stack: the two cross-stream waits per step cost more than
-// the all-gather they hide (profiles/r01_shard_overlap_trace.txt).
+// Chains (smx_tune_fused): 0 select + update per pivot; 1 one fused kernel per pivot (default).
 int g_fused = 1;
 
 // ev (optional): 2 events per step recorded around its update launch.
@@ -1041,15 +1026,9 @@ int smx_tune_set(int32_t variant, int32_t blocks_per_cu_override) {
     return 0;
 }
 
-int64_t smx_tune_fold(int64_t min_bytes) {
-    const int64_t prev = g_fold_min_bytes;
-    if (min_bytes >= 0) g_fold_min_bytes = min_bytes;
-    return prev;
-}
-
 int smx_tune_fused(int32_t on) {
     const int prev = g_fused;
-    if (on >= 0) g_fused = on > 3 ? 3 : on;
+    if (on >= 0) g_fused = on ? 1 : 0;
     return prev;
 }
 
@@ -1483,157 +1462,28 @@ int smx_comm_info(void* comm, int32_t* count, int32_t* rank, int32_t* device) {
 
 namespace {
 // Fused sharded chain, per pivot: k_pack<true> (step k's records -> header + candidate rows)
-// -> one ncclAllGather -> k_update<kShardFused> (merge, sweep, step k+1's records; with
-// smx_tune_fold also step k+1's pack, then the next k_pack is skipped).  Primed by k_la_prime,
-// closed by k_publish.  e_upd: 2k events around the updates.
+// -> one ncclAllGather -> k_update<kShardFused> (merge, sweep, step k+1's records).  Primed by
+// k_la_prime, closed by k_publish.  e_upd: 2k events around the updates.
 int shard_chain_fused(double* buf0, double* buf1, const smx_shape& s, int parity, int k,
                       smx_ctl* ctl, smx_part* parts, double* send, double* recv, int nranks,
                       ncclComm_t comm, int32_t* log, int64_t log_cap, hipEvent_t* e_upd,
                       hipStream_t st) {
     double* T0 = parity ? buf1 : buf0;
-    const bool fold = folds_pack(s);
     int err = launch_prime(T0, s, parity, ctl, parts, st);
     const size_t slot = (size_t)SMX_SHARD_HDR + 2 * (size_t)s.ld;
     for (int step = 0; step < k && !err; ++step) {
         const int p = (parity + step) & 1;
         double* tin = p ? buf1 : buf0;
         double* tout = p ? buf0 : buf1;
-        if (step == 0 || !fold)
-            err = launch_pack<true>(tin, s, p, ctl, parts + (size_t)p * s.nparts, send, st);
+        err = launch_pack<true>(tin, s, p, ctl, parts + (size_t)p * s.nparts, send, st);
         if (!err) err = nccl_err(ncclAllGather(send, recv, slot, ncclFloat64, comm, st));
         if (err) break;
         if (e_upd) (void)hipEventRecord(e_upd[2 * step], st);
         err = launch_update_mode<kShardFused>(tin, tout, s, p, ctl, parts, log, nullptr, log_cap,
-                                              recv, 0, nranks, st, 0, fold ? send : nullptr);
+                                              recv, 0, nranks, st);
         if (e_upd) (void)hipEventRecord(e_upd[2 * step + 1], st);
     }
     if (!err) err = launch_publish(s, (parity + k) & 1, ctl, parts, st);
-    return err;
-}
-
-// The two halves of an overlapped sharded step (also exported for the P-rank simulation tests):
-// ahead = step k+1's records (s.nparts of them, slot parity^1) and, if `pack`, its header and
-// candidate rows into `send`, from T_k and step k's gathered headers; sweep = the update of step
-// k without look-ahead workgroups, leaving `reserve` resident slots free.
-int launch_ahead(const double* T, const smx_shape& s, int parity, const double* recv,
-                 int nranks, smx_ctl* ctl, smx_part* parts, double* send, bool pack,
-                 hipStream_t st) {
-    smx_part* pn = parts + (size_t)(parity ^ 1) * s.nparts;
-    hipLaunchKernelGGL(k_shard_la, dim3(s.nparts), dim3(kUpdBlock), 0, st, T, s.ld, s.rows, s.m,
-                       s.flen, fscan_of(s), s.row0, recv, nranks, ctl, pn, parity ^ 1);
-    if (pack)
-        hipLaunchKernelGGL(k_pack_ahead, dim3(s.nparts), dim3(kUpdBlock), 0, st, T, s.ld, s.rows,
-                           s.m, s.flen, s.row0, recv, nranks, ctl, pn, s.nparts, parity ^ 1,
-                           send);
-    return (int)hipGetLastError();
-}
-
-int launch_sweep(const double* Tin, double* Tout, const smx_shape& s, int parity,
-                 const double* recv, int nranks, smx_ctl* ctl, int32_t* log, int64_t log_cap,
-                 int reserve, hipStream_t st) {
-    smx_shape sy = s;
-    sy.nparts = 0;   // no look-ahead workgroups
-    return launch_update_mode<kShardFused>(Tin, Tout, sy, parity, ctl, nullptr, log, nullptr,
-                                           log_cap, recv, 0, nranks, st, reserve);
-}
-
-// The exchange stream and two events of the overlapped chain, created once per device.
-struct Overlap {
-    hipStream_t s2 = nullptr;
-    hipEvent_t ev_sweep = nullptr, ev_gather = nullptr;
-    uint64_t* sig[2] = {nullptr, nullptr};   // signal memory: sweeps done, gathers done
-    uint64_t seq = 0;                        // next base of the (monotonic) counters
-};
-
-int overlap_for_device(Overlap** out) {
-    static Overlap cache[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
-    Overlap& o = cache[dev];
-    if (!o.s2) {
-        hipError_t e = hipStreamCreateWithFlags(&o.s2, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&o.ev_sweep, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&o.ev_gather, hipEventDisableTiming);
-        if (e != hipSuccess) return (int)e;
-    }
-    *out = &o;
-    return 0;
-}
-
-constexpr int kOverlapParts = 16;   // look-ahead workgroups of the overlapped chain
-
-// Overlapped sharded chain.  recv holds two gather slots (step parity).  Per step k:
-//   S2: wait(T_k ready) -> k_shard_la (records of k+1) -> k_pack_ahead -> all-gather into
-//       recv[(k+1)&1] -> record ev_gather
-//   S1: k_update<kShardFused> without look-ahead workgroups (T_k -> T_{k+1}, pivot from
-//       recv[k&1]) -> wait(ev_gather) -> record ev_sweep
-// S1 waiting for the gather before the next sweep also orders S2's reads of T_k before the
-// sweep that overwrites it.  The last step computes the records of step k (for a continuation)
-// but no pack/gather.
-int shard_chain_overlap(double* buf0, double* buf1, const smx_shape& s, int parity, int k,
-                        smx_ctl* ctl, smx_part* parts, double* send, double* recv, int nranks,
-                        ncclComm_t comm, int32_t* log, int64_t log_cap, hipEvent_t* e_upd,
-                        hipStream_t st, bool values) {
-    Overlap* o = nullptr;
-    int err = overlap_for_device(&o);
-    if (err) return err;
-    for (int q = 0; values && q < 2 && !o->sig[q]; ++q) {   // one 8-B signal each, zeroed
-        hipError_t e = hipExtMallocWithFlags(reinterpret_cast<void**>(&o->sig[q]),
-                                             sizeof(uint64_t), hipMallocSignalMemory);
-        if (e == hipSuccess) e = hipStreamWriteValue64(st, o->sig[q], 0, 0);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            o->sig[q] = nullptr;
-            return (int)e;
-        }
-    }
-    smx_shape sx = s;
-    sx.nparts = s.nparts < kOverlapParts ? s.nparts : kOverlapParts;
-    const int npx = sx.nparts;
-    const size_t slot = (size_t)SMX_SHARD_HDR + 2 * (size_t)s.ld;
-    const size_t rsz = (size_t)nranks * slot;
-    double* T0 = parity ? buf1 : buf0;
-    err = launch_prime(T0, sx, parity, ctl, parts, st);
-    if (!err) err = launch_pack<true>(T0, sx, parity, ctl, parts + (size_t)parity * npx, send, st);
-    if (!err) err = nccl_err(ncclAllGather(send, recv + (size_t)parity * rsz, slot, ncclFloat64,
-                                           comm, st));
-    // `values`: the two cross-stream dependencies as stream memory operations on monotonic
-    // counters (sig[0] = sweeps done + 1, sig[1] = gathers done) instead of events
-    const uint64_t base = o->seq;
-    auto signal_sweep = [&](uint64_t v) {
-        return values ? (int)hipStreamWriteValue64(st, o->sig[0], base + v, 0)
-                      : (int)hipEventRecord(o->ev_sweep, st);
-    };
-    if (!err) err = signal_sweep(1);
-    for (int step = 0; step < k && !err; ++step) {
-        const int p = (parity + step) & 1;
-        double* tin = p ? buf1 : buf0;
-        double* tout = p ? buf0 : buf1;
-        const double* rc = recv + (size_t)p * rsz;
-        double* rn = recv + (size_t)(p ^ 1) * rsz;
-        const bool more = step + 1 < k;
-        err = values ? (int)hipStreamWaitValue64(o->s2, o->sig[0], base + step + 1,
-                                                 hipStreamWaitValueGte, ~0ull)
-                     : (int)hipStreamWaitEvent(o->s2, o->ev_sweep, 0);
-        if (!err) err = launch_ahead(tin, sx, p, rc, nranks, ctl, parts, send, more, o->s2);
-        if (!err && more)
-            err = nccl_err(ncclAllGather(send, rn, slot, ncclFloat64, comm, o->s2));
-        if (!err)
-            err = values ? (int)hipStreamWriteValue64(o->s2, o->sig[1], base + step + 1, 0)
-                         : (int)hipEventRecord(o->ev_gather, o->s2);
-        if (err) break;
-        if (e_upd) (void)hipEventRecord(e_upd[2 * step], st);
-        err = launch_sweep(tin, tout, s, p, rc, nranks, ctl, log, log_cap, npx, st);
-        if (e_upd) (void)hipEventRecord(e_upd[2 * step + 1], st);
-        if (!err)
-            err = values ? (int)hipStreamWaitValue64(st, o->sig[1], base + step + 1,
-                                                     hipStreamWaitValueGte, ~0ull)
-                         : (int)hipStreamWaitEvent(st, o->ev_gather, 0);
-        if (!err) err = signal_sweep(step + 2);
-    }
-    o->seq = base + k + 2;
-    if (!err) err = launch_publish(sx, (parity + k) & 1, ctl, parts, st);
     return err;
 }
 
@@ -1659,9 +1509,6 @@ int launch_shard_chain(double* buf0, double* buf1, const smx_shape& s, int parit
                        smx_ctl* ctl, smx_part* parts, double* send, double* recv, int nranks,
                        ncclComm_t comm, int32_t* log, int64_t log_cap, hipEvent_t* ev,
                        hipStream_t st) {
-    if (g_fused >= 2 && k > 0)
-        return shard_chain_overlap(buf0, buf1, s, parity, k, ctl, parts, send, recv, nranks, comm,
-                                   log, log_cap, ev, st, g_fused == 3);
     if (g_fused && k > 0)
         return shard_chain_fused(buf0, buf1, s, parity, k, ctl, parts, send, recv, nranks, comm,
                                  log, log_cap, ev, st);
@@ -1719,28 +1566,9 @@ int smx_shard_fused_finish(const double* Tin, double* Tout, const double* recv, 
     if (ev_before) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(ev_before), S(stream));
     const int err = launch_update_mode<kShardFused>(Tin, Tout, *shape, parity & 1, ctl, parts,
                                                     log, nullptr, log_cap, recv, 0, nranks,
-                                                    S(stream), 0,
-                                                    folds_pack(*shape) ? send : nullptr);
+                                                    S(stream));
     if (ev_after) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(ev_after), S(stream));
     return err;
-}
-
-int smx_shard_folds_pack(const smx_shape* shape) {
-    return shape_ok(shape) && folds_pack(*shape) ? 1 : 0;
-}
-
-int smx_shard_ahead(const double* T, const smx_shape* shape, int32_t parity, const double* recv,
-                    int32_t nranks, smx_ctl* ctl, smx_part* parts, double* send, void* stream) {
-    if (!shape_ok(shape) || nranks < 1) return (int)hipErrorInvalidValue;
-    return launch_ahead(T, *shape, parity & 1, recv, nranks, ctl, parts, send, true, S(stream));
-}
-
-int smx_shard_sweep(const double* Tin, double* Tout, const double* recv, int32_t nranks,
-                    const smx_shape* shape, int32_t parity, smx_ctl* ctl, int32_t* log,
-                    int64_t log_cap, void* stream) {
-    if (!shape_ok(shape) || Tin == Tout || nranks < 1) return (int)hipErrorInvalidValue;
-    return launch_sweep(Tin, Tout, *shape, parity & 1, recv, nranks, ctl, log, log_cap, 0,
-                        S(stream));
 }
 
 int smx_copy_probe(const double* src, double* dst, int64_t ndoubles, int32_t variant,

@@ -1,4 +1,4 @@
-// smx_lookahead.hpp -- the fused chain's look-ahead: next-step records from T_k, decision, prime/publish, pack
+// smx_lookahead.hpp -- the fused chain's look-ahead: next-step records from T_k, decision, prime/publish
 // Part of libsmx (compiled as one translation unit by smx_kernels.hip; not a standalone header).
 #pragma once
 #pragma clang fp contract(off)
@@ -219,87 +219,6 @@ __global__ __launch_bounds__(kWave) void k_publish(const smx_part* __restrict__ 
         ctl->negb[parity] = nb;
         ctl->negb[parity ^ 1] = SMX_NONE;
         ctl->negf[parity ^ 1] = SMX_NONE;
-    }
-}
-
-// Header + candidate rows of step k+1 (layout of k_pack) from step k+1's records (`parts`, slot
-// `slot`, nparts of them) and T_k with step k's pivot (r_local, c, e, prow): every value is
-// nv(T_k, pivot k), i.e. exactly T_{k+1}.  Workgroup bidx of nblk; all threads of the group call.
-__device__ void pack_ahead(const double* __restrict__ T, int64_t ld, int rows, int m, int row0,
-                           int r_local, int c, double e, const double* __restrict__ prow,
-                           const smx_ctl* __restrict__ ctl, const smx_part* __restrict__ parts,
-                           int nparts, int slot, double* __restrict__ send, int bidx, int nblk) {
-    __shared__ int s_rows[2];
-    __shared__ int s_hdr_i[4];
-    __shared__ double s_hdr_d[2];
-    __shared__ int s_tmp[kUpdBlock / kWave];
-    const int tid = threadIdx.x;
-    const int cn = ctl->negf[slot];   // step k+1's entering column (look-ahead workgroup 0)
-    if (tid < kWave) {
-        int nb = SMX_NONE;
-        First f{SMX_NONE, 0.0};
-        Cand b = cand_none();
-        for (int k = tid; k < nparts; k += kWave) {
-            const smx_part p = parts[k];
-            nb = min(nb, p.p1col);
-            if (p.first < f.idx) {
-                f.idx = p.first;
-                f.v = p.first_v;
-            }
-            Cand o{p.best_cls, p.best_i, p.best_v};
-            if (better(o, b)) b = o;
-        }
-        nb = wave_min_int(nb);
-        f = wave_first(f);
-        b = wave_best(b);
-        if (nb != SMX_NONE || cn == SMX_NONE) {   // phase 1 / no entering column: no ratio test
-            f = First{SMX_NONE, 0.0};
-            b = cand_none();
-        }
-        if (tid == 0) {
-            s_rows[0] = (f.idx != SMX_NONE && isnan(f.v)) ? f.idx - row0 : -1;     // row A
-            s_rows[1] = (nb != SMX_NONE) ? nb - row0 : (b.cls < 3 ? b.idx - row0 : -1);
-            s_hdr_i[0] = nb;
-            s_hdr_i[1] = f.idx;
-            s_hdr_i[2] = b.cls;
-            s_hdr_i[3] = b.idx;
-            s_hdr_d[0] = f.v;
-            s_hdr_d[1] = b.v;
-        }
-    }
-    __syncthreads();
-    const int ra = s_rows[0], rb = s_rows[1];
-    const int nb = s_hdr_i[0];
-    if (bidx == 0) {
-        int p1 = SMX_NONE;   // phase 1 (simplex.py:81-85) on the new values of the owner's row
-        if (nb != SMX_NONE) {
-            const int il = nb - row0;
-            const double pci = T[(int64_t)il * ld + c];
-            for (int j = tid; j < m; j += kUpdBlock) {
-                if (nv(T, ld, r_local, c, e, prow, il, j, pci) > 0.0) {
-                    p1 = j;
-                    break;
-                }
-            }
-            p1 = block_min_int<kUpdBlock>(p1, s_tmp);
-        }
-        if (tid == 0) {
-            send[0] = (double)nb;
-            send[1] = (double)s_hdr_i[1];
-            send[2] = s_hdr_d[0];
-            send[3] = (double)s_hdr_i[2];
-            send[4] = (double)s_hdr_i[3];
-            send[5] = s_hdr_d[1];
-            send[6] = (double)cn;
-            send[7] = (double)p1;
-        }
-    }
-    const int C = m + 1;
-    const double pca = ra >= 0 ? T[(int64_t)ra * ld + c] : 0.0;
-    const double pcb = rb >= 0 ? T[(int64_t)rb * ld + c] : 0.0;
-    for (int j = bidx * kUpdBlock + tid; j < C; j += nblk * kUpdBlock) {
-        if (ra >= 0) send[SMX_SHARD_HDR + j] = nv(T, ld, r_local, c, e, prow, ra, j, pca);
-        if (rb >= 0) send[SMX_SHARD_HDR + ld + j] = nv(T, ld, r_local, c, e, prow, rb, j, pcb);
     }
 }
 

@@ -1,4 +1,4 @@
-// smx_shard.hpp -- row-sharded exchange: k_pack, k_merge, the overlapped chain's k_shard_la / k_pack_ahead
+// smx_shard.hpp -- row-sharded exchange: k_pack, k_merge
 // Part of libsmx (compiled as one translation unit by smx_kernels.hip; not a standalone header).
 #pragma once
 #pragma clang fp contract(off)
@@ -114,59 +114,6 @@ __global__ __launch_bounds__(kWave) void k_merge(const double* __restrict__ recv
     if (ctl->term || threadIdx.x != 0) return;
     const ShardDecision d = merge_headers(recv, nranks, ld, m, flen);
     publish_shard_decision(d, recv, ctl, log, log_cap, false);
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Overlapped sharded chain (smx_shard_run with the fused chain on): while k_update<kShardFused>
-// sweeps T_k -> T_{k+1} on the solver stream, the exchange stream computes step k+1's records
-// (k_shard_la) and header + candidate rows (k_pack_ahead) from T_k and step k's gathered pivot
-// row with the update's own expression (nv), then all-gathers them -- so the collective runs
-// under the sweep.  Both kernels re-derive step k's decision from the gathered headers
-// (merge_headers is a pure function of recv) and do nothing when it is terminal.
-__device__ __forceinline__ bool merged_pivot(const double* __restrict__ recv, int nranks,
-                                             int64_t ld, int m, int flen, int* s_dec,
-                                             int64_t* s_off) {
-    if (threadIdx.x == 0) {
-        const ShardDecision d = merge_headers(recv, nranks, ld, m, flen);
-        s_dec[0] = d.status;
-        s_dec[1] = d.r;
-        s_dec[2] = d.c;
-        *s_off = d.off;
-    }
-    __syncthreads();
-    return s_dec[0] == SMX_PIVOT;
-}
-
-__global__ __launch_bounds__(kUpdBlock) void k_shard_la(const double* __restrict__ T, int64_t ld,
-                                                        int rows, int m, int flen, int fscan,
-                                                        int row0, const double* __restrict__ recv,
-                                                        int nranks, smx_ctl* __restrict__ ctl,
-                                                        smx_part* __restrict__ out, int slot) {
-    __shared__ int s_dec[3];
-    __shared__ int64_t s_off;
-    if (ctl->term) return;
-    if (!merged_pivot(recv, nranks, ld, m, flen, s_dec, &s_off)) return;
-    const int r = s_dec[1], c = s_dec[2];
-    const double* prow = recv + s_off;
-    const int r_local = (r >= row0 && r < row0 + rows) ? r - row0 : -1;
-    la_partial<kUpdBlock, true>(T, ld, rows, m, fscan, row0, r_local, c, prow[c], prow, out,
-                                blockIdx.x, gridDim.x, ctl, slot);
-}
-
-__global__ __launch_bounds__(kUpdBlock) void k_pack_ahead(
-    const double* __restrict__ T, int64_t ld, int rows, int m, int flen, int row0,
-    const double* __restrict__ recv, int nranks, const smx_ctl* __restrict__ ctl,
-    const smx_part* __restrict__ parts, int nparts, int slot, double* __restrict__ send) {
-    __shared__ int s_dec[3];
-    __shared__ int64_t s_off;
-    if (ctl->term) return;
-    if (!merged_pivot(recv, nranks, ld, m, flen, s_dec, &s_off)) return;
-    const int r = s_dec[1], c = s_dec[2];
-    const double* prow = recv + s_off;
-    const int r_local = (r >= row0 && r < row0 + rows) ? r - row0 : -1;
-    pack_ahead(T, ld, rows, m, row0, r_local, c, prow[c], prow, ctl, parts, nparts, slot, send,
-               blockIdx.x, gridDim.x);
 }
 
 }  // namespace

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kUpdBlock) void k_update(
     int n, int m, int flen, int fscan, int row0, int parity, smx_ctl* __restrict__ ctl,
     const smx_part* __restrict__ parts, int nparts, int32_t* __restrict__ log,
     double* __restrict__ xhist, int64_t log_cap, const double* __restrict__ recv, int forced_r,
-    int forced_c, double* __restrict__ send) {
+    int forced_c) {
     __shared__ int s_dec[3];
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
@@ -212,24 +212,6 @@ __global__ __launch_bounds__(kUpdBlock) void k_update(
         la_partial<kUpdBlock, true>(Tin, ld, rows_local, m, fscan, row0, r_local, c, e, prow,
                                     const_cast<smx_part*>(parts) + (size_t)(parity ^ 1) * nparts,
                                     blockIdx.x, nparts, ctl, parity ^ 1);
-        if (MODE == kShardFused && send != nullptr) {
-            // The last look-ahead workgroup to finish packs step k+1's header and candidate
-            // rows into the send slot (values of T_{k+1} via nv), so a sharded pivot is this
-            // kernel + the all-gather.  nparts counter atomics, not one per workgroup.
-            __shared__ int s_last;
-            __syncthreads();
-            if (tid == 0) {
-                __threadfence();   // release this workgroup's record (and negf from group 0)
-                s_last = atomicAdd(&ctl->nla, 1) == nparts - 1;
-            }
-            __syncthreads();
-            if (s_last) {
-                __threadfence();   // acquire the other workgroups' records
-                pack_ahead(Tin, ld, rows_local, m, row0, r_local, c, e, prow, ctl,
-                           parts + (size_t)(parity ^ 1) * nparts, nparts, parity ^ 1, send, 0, 1);
-                if (tid == 0) ctl->nla = 0;
-            }
-        }
         SMX_STAMP(2);
         if (!la_sweep) return;
     }

@@ -113,8 +113,7 @@ EXPORTS = (
     "smx_comm_unique_id", "smx_comm_init", "smx_comm_destroy",
     "smx_shard_run", "smx_shard_run_timed", "smx_shard_pack", "smx_shard_merge", "smx_shard_update", "smx_shard_begin",
     "smx_shard_finish", "smx_shard_fused_prime", "smx_shard_fused_begin",
-    "smx_shard_fused_finish", "smx_fused_publish", "smx_shard_ahead", "smx_shard_sweep",
-    "smx_copy_probe", "smx_shard_folds_pack", "smx_tune_fold",
+    "smx_shard_fused_finish", "smx_fused_publish", "smx_copy_probe",
     "smx_tune_resident", "smx_tune_resident_overlap", "smx_tune_resident_timeout", "smx_resident_trace", "smx_resident_bytes",
     "smx_resident_run", "smx_fastdiv_check", "smx_fastdiv_check_bounded",
     "smx_tune_block", "smx_tune_block_form", "smx_tune_block_planner", "smx_block_bytes", "smx_block_run", "smx_block_run_timed",
@@ -210,11 +209,7 @@ def load():
         "smx_shard_fused_finish": ([vp, vp, vp, i32, sp, i32, vp, vp, vp, vp, i64, vp, vp, vp],
                                    ctypes.c_int),
         "smx_fused_publish": ([sp, i32, vp, vp, vp], ctypes.c_int),
-        "smx_shard_ahead": ([vp, sp, i32, vp, i32, vp, vp, vp, vp], ctypes.c_int),
-        "smx_shard_sweep": ([vp, vp, vp, i32, sp, i32, vp, vp, i64, vp], ctypes.c_int),
         "smx_copy_probe": ([vp, vp, i64, i32, vp], ctypes.c_int),
-        "smx_shard_folds_pack": ([sp], ctypes.c_int),
-        "smx_tune_fold": ([i64], ctypes.c_int64),
         "smx_tune_resident": ([i32], ctypes.c_int),
         "smx_tune_resident_overlap": ([i32], ctypes.c_int),
         "smx_tune_resident_timeout": ([i64], ctypes.c_int64),

@@ -95,39 +95,27 @@ class HipShardBackend(_ShardState):
 
     ``fused`` (default: the library's chain mode, smx_tune_fused): a pivot is fused pack ->
     all-gather -> fused update, with the next step's look-ahead records written by the update
-    (no select kernel); otherwise select + pack -> all-gather -> update.  ``overlap`` (fused
-    only, off by default): the native chain (run_native*) runs the next step's look-ahead and
-    all-gather on a second stream under the sweep -- slower on this stack, see DESIGN.md §12."""
+    (no select kernel); otherwise select + pack -> all-gather -> update."""
 
     def __init__(self, local_T: np.ndarray, n: int, m: int, flen: int, row0: int, world: int,
-                 device=None, log_cap: int = 1 << 16, fused: bool | None = None,
-                 overlap: bool = False):
+                 device=None, log_cap: int = 1 << 16, fused: bool | None = None):
         self.dev = DeviceTableau(local_T, n, m, flen, device=device, row0=row0, n_global=n,
                                  log_cap=log_cap)
         self.world = world
         self.slot = ops.shard_slot(self.dev.ld)
         with torch.cuda.stream(self.dev.stream):
             self.send = torch.zeros(self.slot, dtype=torch.float64, device=self.dev.device)
-            # two gather slots: the overlapped native chain alternates them by step parity;
-            # the per-step path (begin / all-gather / finish) uses the first
-            self._recv2 = torch.zeros(2 * world * self.slot, dtype=torch.float64,
-                                      device=self.dev.device)
-            self.recv = self._recv2[:world * self.slot]
+            self.recv = torch.zeros(world * self.slot, dtype=torch.float64,
+                                    device=self.dev.device)
         self._shape = ops.make_shape(self.dev.shape)
         self.fused = _lib.fused_enabled() if fused is None else bool(fused)
-        # True / "events": the exchange stream synchronised by events; "values": by stream
-        # memory operations on device counters
-        self.overlap = overlap if (overlap and self.fused) else False
         self._records = False   # look-ahead records of step dev.step are in dev.parts
-        self._packed = False    # overlap form: send already holds step dev.step's pack
 
     def begin(self) -> None:
         d = self.dev
         L = _lib.load()
         if self.fused:
             p = d.step & 1
-            if self._packed:
-                return          # packed by the previous finish (fused update / shard_ahead)
             if not self._records:
                 _lib.check(L.smx_shard_fused_prime(
                     d.buf[p].data_ptr(), ctypes.byref(self._shape), p, d.ctl.data_ptr(),
@@ -146,28 +134,7 @@ class HipShardBackend(_ShardState):
     def finish(self, ev_before=None, ev_after=None) -> None:
         d = self.dev
         p = d.step & 1
-        if self.overlap:
-            L = _lib.load()
-            # step k+1's records + pack from T_k (the native chain runs this on its exchange
-            # stream, concurrently with the sweep), then step k's sweep
-            _lib.check(L.smx_shard_ahead(
-                d.buf[p].data_ptr(), ctypes.byref(self._shape), p, self.recv.data_ptr(),
-                self.world, d.ctl.data_ptr(), d.parts.data_ptr(), self.send.data_ptr(),
-                d.stream.cuda_stream), "smx_shard_ahead")
-            if ev_before is not None:
-                ev_before.record(d.stream)
-            _lib.check(L.smx_shard_sweep(
-                d.buf[p].data_ptr(), d.buf[p ^ 1].data_ptr(), self.recv.data_ptr(), self.world,
-                ctypes.byref(self._shape), p, d.ctl.data_ptr(), d.log.data_ptr(), d.log_cap,
-                d.stream.cuda_stream), "smx_shard_sweep")
-            if ev_after is not None:
-                ev_after.record(d.stream)
-            self._packed = True
-            d.step += 1
-            d._pending = True
-            return
         if self.fused:
-            # the update's last look-ahead workgroup also packs the next step into send
             _lib.check(_lib.load().smx_shard_fused_finish(
                 d.buf[p].data_ptr(), d.buf[p ^ 1].data_ptr(), self.recv.data_ptr(), self.world,
                 ctypes.byref(self._shape), p, d.ctl.data_ptr(), d.parts.data_ptr(),
@@ -175,7 +142,6 @@ class HipShardBackend(_ShardState):
                 ev_before.cuda_event if ev_before is not None else None,
                 ev_after.cuda_event if ev_after is not None else None, d.stream.cuda_stream),
                 "smx_shard_fused_finish")
-            self._packed = bool(_lib.load().smx_shard_folds_pack(ctypes.byref(self._shape)))
             d.step += 1
             d._pending = True
             return
@@ -194,18 +160,17 @@ class HipShardBackend(_ShardState):
         chain mode meanwhile (smx_tune_fused is process-wide); k pivots are booked on leaving."""
         d = self.dev
         L = _lib.load()
-        mode = (3 if self.overlap == "values" else 2) if self.overlap else 1
-        prev = L.smx_tune_fused(mode if self.fused else 0)
+        prev = L.smx_tune_fused(1 if self.fused else 0)
         try:
             yield (d.buf[0].data_ptr(), d.buf[1].data_ptr(), ctypes.byref(self._shape),
                    d.step & 1, k, d.ctl.data_ptr(), d.parts.data_ptr(), self.send.data_ptr(),
-                   self._recv2.data_ptr(), self.world, comm.handle, d.log.data_ptr(), d.log_cap,
+                   self.recv.data_ptr(), self.world, comm.handle, d.log.data_ptr(), d.log_cap,
                    d.stream.cuda_stream)
         finally:
             L.smx_tune_fused(prev)
         d.step += k
         d._pending = True
-        self._records = self._packed = False   # the native chain may keep fewer records
+        self._records = False   # the next begin() primes again
 
     def run_native(self, k: int, comm: "RcclComm") -> None:
         """k pivots, all-gathers issued by libsmx.so on the solver stream (no host sync)."""
@@ -633,7 +598,7 @@ def bench_main(args, metric, peak_gbs, cpu_baseline_fn=None, load_traffic=None,
                        "pivots_per_sweep": pivots if block else 1,
                        "kernels_per_pivot": (2 * args.steps + nsw) / args.steps if block
                        else (2 if be.fused else 3),
-                       "gather_overlapped_with_sweep": False if block else be.overlap,
+                       "gather_overlapped_with_sweep": False,
                        "exchange": "light" if light else "full",
                        "collectives_per_pivot": 2 if light else 1,
                        "exchange_bytes_per_pivot_per_rank": xbytes},

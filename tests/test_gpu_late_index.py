@@ -416,14 +416,14 @@ def _modes():
     return list(MODES)
 
 
-@pytest.mark.parametrize("mode", ["overlap", "fused", "unfused"])
+@pytest.mark.parametrize("mode", ["fused", "unfused"])
 @pytest.mark.parametrize("name", sorted(li.SHARDED))
 def test_hip_shards_vs_oracle(name, mode):
     """The one-pivot shard chain: the live rows owned by the last rank (gnegb / owner_b of the
     merged decision never rank 0's) and straddling two ranks (the owner changes along the
     chain)."""
     from test_gpu_sharded import _simulate
-    assert mode in _modes() and len(_modes()) == 3
+    assert mode in _modes() and len(_modes()) == 2
     args, world, k, _ = li.SHARDED[name]
     n, m = args[1:3]
     ref = li.reference(name)
@@ -431,7 +431,7 @@ def test_hip_shards_vs_oracle(name, mode):
     _shards_same_as_oracle(states, logs, tables, full, ref, n, m, (name, mode))
 
 
-@pytest.mark.parametrize("mode", ["overlap", "fused", "unfused"])
+@pytest.mark.parametrize("mode", ["fused", "unfused"])
 @pytest.mark.parametrize("world", [2, 4])
 def test_hip_shards_planted_decisions(world, mode):
     """The planted tables at 300 x 260 on ranks of 150 and of 75 rows: the tie with r1 and r2 on

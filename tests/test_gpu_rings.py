@@ -428,7 +428,7 @@ def test_multi_read_xhist_refuses_pivots_that_left_the_ring():
 
 
 # -- one-pivot shards ----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode", ["overlap", "fused", "unfused"])
+@pytest.mark.parametrize("mode", ["fused", "unfused"])
 @pytest.mark.parametrize("cap", [5, 64])
 def test_one_pivot_shards_log_ring(cap, mode):
     """HipShardBackend takes no x-history ring: its log against the simulation on every rank, and
@@ -437,12 +437,11 @@ def test_one_pivot_shards_log_ring(cap, mode):
     from simplex_mi355x.sharded import HipShardBackend, row_range
     from test_gpu_sharded import MODES
     T, n, m = lp_case("u0")
-    fused_, ovl = MODES[mode]
     bes = []
     for p in range(3):
         lo, hi = row_range(n, p, 3)
         local = np.concatenate([T[lo:hi], T[n:n + 1]], axis=0)
-        bes.append(HipShardBackend(local, n, m, m, lo, 3, log_cap=cap, fused=fused_, overlap=ovl))
+        bes.append(HipShardBackend(local, n, m, m, lo, 3, log_cap=cap, fused=MODES[mode]))
         poison(bes[-1].dev)
     asked = 0
     for k in (10, 30):

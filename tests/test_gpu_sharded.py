@@ -1,8 +1,7 @@
 """GPU: the HIP shard kernels for P simulated ranks in one process on one device (the all-gather
-done by a device copy), against the unsharded C oracle, bit for bit -- all three pivot forms:
-unfused (k_select/k_pack/k_update<kShard>), fused (k_la_prime/k_pack<fused>/
-k_update<kShardFused>) and the overlapped chain's halves (k_shard_la + k_pack_ahead, then the
-sweep without look-ahead workgroups).  The native RCCL driver is covered at world size 1
+done by a device copy), against the unsharded C oracle, bit for bit -- both pivot forms:
+unfused (k_select/k_pack/k_update<kShard>) and fused (k_la_prime/k_pack<fused>/
+k_update<kShardFused>).  The native RCCL driver is covered at world size 1
 (tools/check_native_shard.py) and the multi-process protocol by the gloo tests."""
 from __future__ import annotations
 
@@ -19,10 +18,10 @@ def _need_gpu():
         pytest.skip("needs an MI355X")
 
 
-MODES = {"overlap": (True, True), "fused": (True, False), "unfused": (False, False)}
+MODES = {"fused": True, "unfused": False}   # HipShardBackend(fused=...)
 
 
-def _simulate(T, n, m, k, P, mode="overlap", bes=None):
+def _simulate(T, n, m, k, P, mode="fused", bes=None):
     import torch
     from simplex_mi355x.sharded import HipShardBackend, row_range
     if bes is None:
@@ -30,8 +29,7 @@ def _simulate(T, n, m, k, P, mode="overlap", bes=None):
         for p in range(P):
             lo, hi = row_range(n, p, P)
             local = np.concatenate([T[lo:hi], T[n:n + 1]], axis=0)
-            fused, overlap = MODES[mode]
-            bes.append(HipShardBackend(local, n, m, m, lo, P, fused=fused, overlap=overlap))
+            bes.append(HipShardBackend(local, n, m, m, lo, P, fused=MODES[mode]))
     for _ in range(k):
         for be in bes:
             with be.stream_ctx():
@@ -121,7 +119,7 @@ def test_hip_shards_fused_then_unfused():
         d = be.dev
         _lib.check(L.smx_fused_publish(ctypes.byref(be._shape), d.step & 1, d.ctl.data_ptr(),
                                        d.parts.data_ptr(), d.stream.cuda_stream), "publish")
-        be.fused = be.overlap = False
+        be.fused = False
     torch.cuda.synchronize()
     states, logs, tables, full, _ = _simulate(T, n, m, 45, P, bes=bes)
     Tref, st, done, log = c_oracle.run(T, n, m, m, 82, threads=8)
@@ -164,22 +162,13 @@ def test_hip_shards_nan_first_candidate(mode, case, P):
     assert np.array_equal(np.isnan(full[:n]), np.isnan(Tref[:n]))
 
 
-@pytest.mark.parametrize("kind,n", [("uniform", 4095), ("mixed", 4096)])
-def test_hip_shards_folded_pack(kind, n):
-    """smx_tune_fold(0): the fused update's last look-ahead workgroup packs the next step."""
-    from oracle import c_oracle
-    from simplex_mi355x import _lib, lp
+def test_tune_fused_is_two_valued():
+    """smx_tune_fused keeps 0 or 1: a caller that still asks for 2 gets the plain fused chain."""
+    from simplex_mi355x import _lib
     L = _lib.load()
-    m, k, P = 4095, 24, 2
-    prev = L.smx_tune_fold(0)
+    prev = L.smx_tune_fused(-1)
     try:
-        T = lp.dense_tableau(kind, 7, n, m)
-        states, logs, tables, full, bes = _simulate(T, n, m, k, P, "fused")
-        assert all(L.smx_shard_folds_pack(__import__("ctypes").byref(b._shape)) for b in bes)
+        L.smx_tune_fused(2)
+        assert L.smx_tune_fused(-1) == 1
     finally:
-        L.smx_tune_fold(prev)
-    Tref, st, done, log = c_oracle.run(T, n, m, m, k, threads=8)
-    for s_, lg in zip(states, logs):
-        assert s_["npivots"] == done
-        assert np.array_equal(lg, log)
-    assert np.array_equal(full[:n].view(np.int64), Tref[:n].view(np.int64))
+        L.smx_tune_fused(prev)

@@ -24,12 +24,12 @@ cases = (("uniform", 1023, 777, 120), ("mixed", 600, 500, 150),
          ("mixed", 4095, 4095, 40))
 # the same chain with HIP events around every update (smx_shard_run_timed): the oracle takes all 25
 timed_case = ("uniform", 40, 30, 25)
-modes = (("overlap", True, True), ("fused", True, False), ("unfused", False, False))
-for (mode, fused, overlap), (kind, n, m, k) in [(md, c) for md in modes
-                                                for c in cases + (timed_case,)]:
+modes = (("fused", True), ("unfused", False))
+for (mode, fused), (kind, n, m, k) in [(md, c) for md in modes
+                                       for c in cases + (timed_case,)]:
     timed = (kind, n, m, k) == timed_case
     T = lp.dense_tableau(kind, 5, n, m)
-    be = HipShardBackend(T, n, m, m, 0, 1, device="cuda:0", fused=fused, overlap=overlap)
+    be = HipShardBackend(T, n, m, m, 0, 1, device="cuda:0", fused=fused)
     comm = RcclComm()
     if timed:
         upd, tot = be.run_native_timed(k, comm)
