@@ -875,7 +875,9 @@ __device__ __forceinline__ bool blk_step_body(
 #pragma unroll
         for (int q = 0; q < D; ++q) blk_pin(mqr[q]);
     }
-    // this block's first D pivots (s_pv is complete up to D since the decision)
+    // this block's first D pivots (s_pv is complete up to D since the decision).  Only the
+    // SH = false chains of prv read them, but blk_pv_regs pins its LDS reads, so they are compiled
+    // into the SH = true kernels too: taking them out there changes all 24 of those kernels.
     bool okD = true;
     const BlkPiv pvD = blk_pv_regs<D>(s_pv, &okD);
     auto prv = [&](int j) -> double {

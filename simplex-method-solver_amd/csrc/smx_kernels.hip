@@ -864,8 +864,9 @@ int launch_block_chain(double* buf0, double* buf1, const smx_shape& s, int parit
         done += Pb;
         ++bn;
     }
-    if (err) return err;
-    return bn == 0 ? launch_blk_publish(sh, s, p, bn, ctl, bp, st) : 0;   // (k = 0: no block)
+    // every entry point returns or refuses k = 0 before this, so at least one block ran and the
+    // last block's pivot-column pass has published the chain
+    return err;
 }
 
 bool block_args_ok(const smx_shape* shape, int k, int P, const void* blk, int64_t blk_bytes) {
@@ -1958,7 +1959,8 @@ bool mshard_args_ok(const smx_rank* ranks, int32_t nranks, int32_t k, int32_t pi
     return true;
 }
 
-// Every launch of k chained pivots on every rank, enqueued from this thread (smx_mshard_run)
+// Every launch of k chained pivots on every rank, enqueued from this thread, with the copy
+// exchange (smx_mshard_run's RCCL exchange runs launch_block_chain on one thread per rank).
 // ev_ext: the copy exchange's 2 * nranks events created by the caller, or NULL: created and
 // destroyed here.
 // pool (graph capture, one-device copy exchange only): every event record of the exchange takes
@@ -1966,8 +1968,8 @@ bool mshard_args_ok(const smx_rank* ranks, int32_t nranks, int32_t k, int32_t pi
 // each rank's events once per pivot and crashed the host process in smx_mshard_graph_create,
 // gpurun_out r04g / r04h); `pool_n` events, created by the caller on ranks[0]'s device.
 int mshard_enqueue(const smx_rank* ranks, int32_t nranks, int32_t parity, int32_t k,
-                   int32_t pivots, int32_t exchange, hipEvent_t* ev_ext = nullptr,
-                   hipEvent_t* pool = nullptr, int pool_n = 0) {
+                   int32_t pivots, hipEvent_t* ev_ext = nullptr, hipEvent_t* pool = nullptr,
+                   int pool_n = 0) {
     int dev0 = 0;
     (void)hipGetDevice(&dev0);
     const size_t slot = (size_t)SMX_SHARD_HDR + 2 * (size_t)ranks[0].shape.ld;
@@ -1977,7 +1979,7 @@ int mshard_enqueue(const smx_rank* ranks, int32_t nranks, int32_t parity, int32_
     int err = 0;
     for (int q = 0; q < nranks && !err; ++q) {
         bp[q] = blk_ptrs(ranks[q].shape, static_cast<char*>(ranks[q].blk));
-        if (exchange == SMX_XCHG_COPY && !ev_ext) {
+        if (!ev_ext) {
             err = (int)hipSetDevice(ranks[q].device);
             if (!err) err = (int)hipEventCreateWithFlags(&ev[2 * q], hipEventDisableTiming);
             if (!err) err = (int)hipEventCreateWithFlags(&ev[2 * q + 1], hipEventDisableTiming);
@@ -1988,17 +1990,14 @@ int mshard_enqueue(const smx_rank* ranks, int32_t nranks, int32_t parity, int32_
         return S(ranks[q].stream);
     };
     auto buf = [&](int q, int p) { return p ? ranks[q].buf1 : ranks[q].buf0; };
-    // light exchange (RCCL only; the copy exchange always moves whole slots)
-    const bool light = exchange == SMX_XCHG_RCCL && xchg_light(nranks);
-    // copy exchange on one device: one gather launch on ranks[0]'s stream (k_mshard_gather)
-    bool one_dev = exchange == SMX_XCHG_COPY && nranks <= kMsMaxRanks;
+    // ranks on one device: one gather launch on ranks[0]'s stream (k_mshard_gather)
+    bool one_dev = nranks <= kMsMaxRanks;
     for (int q = 1; q < nranks; ++q) one_dev = one_dev && ranks[q].device == ranks[0].device;
     MsSlots ms{};
     for (int q = 0; q < nranks && one_dev; ++q) {
         ms.src[q] = ranks[q].send;
         ms.dst[q] = ranks[q].recv;
     }
-    auto xrow = [&](int q) { return ranks[q].recv + (size_t)nranks * SMX_SHARD_HDR; };
     for (int q = 0; q < nranks && !err; ++q) {
         hipStream_t st = on(q);
         err = launch_blk_prime(true, buf(q, parity & 1), ranks[q].shape, parity & 1, parity & 1,
@@ -2012,36 +2011,7 @@ int mshard_enqueue(const smx_rank* ranks, int32_t nranks, int32_t parity, int32_
                 err = launch_bsh_pack(l - 1, buf(q, p), ranks[q].shape, Pb, bn, ranks[q].ctl,
                                       bp[q], ranks[q].send, on(q));
             if (err) break;
-            if (exchange == SMX_XCHG_RCCL && light) {
-                // grouped header all-gather, every rank's pick, grouped max all-reduce of a row
-                ncclResult_t rr = ncclGroupStart();
-                for (int q = 0; q < nranks && rr == ncclSuccess; ++q)
-                    rr = ncclAllGather(ranks[q].send, ranks[q].recv, SMX_SHARD_HDR, ncclFloat64,
-                                       reinterpret_cast<ncclComm_t>(ranks[q].comm), on(q));
-                ncclResult_t re = ncclGroupEnd();
-                if (rr == ncclSuccess) rr = re;
-                for (int q = 0; q < nranks && rr == ncclSuccess && !err; ++q)
-                    err = launch_bsh_pick(ranks[q].recv, ranks[q].shape, nranks, q, ranks[q].send,
-                                          xrow(q), on(q));
-                if (rr == ncclSuccess && !err) {
-                    rr = ncclGroupStart();
-                    for (int q = 0; q < nranks && rr == ncclSuccess; ++q)
-                        rr = ncclAllReduce(xrow(q), xrow(q), (size_t)ranks[q].shape.ld, ncclInt64,
-                                           ncclMax, reinterpret_cast<ncclComm_t>(ranks[q].comm),
-                                           on(q));
-                    re = ncclGroupEnd();
-                    if (rr == ncclSuccess) rr = re;
-                }
-                if (rr != ncclSuccess) err = -1000 - (int)rr;
-            } else if (exchange == SMX_XCHG_RCCL) {   // one grouped all-gather of the slots
-                ncclResult_t rr = ncclGroupStart();
-                for (int q = 0; q < nranks && rr == ncclSuccess; ++q)
-                    rr = ncclAllGather(ranks[q].send, ranks[q].recv, slot, ncclFloat64,
-                                       reinterpret_cast<ncclComm_t>(ranks[q].comm), on(q));
-                const ncclResult_t re = ncclGroupEnd();
-                if (rr == ncclSuccess) rr = re;
-                if (rr != ncclSuccess) err = -1000 - (int)rr;
-            } else if (one_dev) {
+            if (one_dev) {
                 // ranks[0]'s stream waits for every pack, gathers every slot into every recv in
                 // one launch, and every other rank waits for that launch: 3N - 1 host calls per
                 // pivot.  A rank's next pack follows its wait, so no slot is overwritten early.
@@ -2093,9 +2063,7 @@ int mshard_enqueue(const smx_rank* ranks, int32_t nranks, int32_t parity, int32_
             for (int q = 0; q < nranks && !err; ++q)
                 err = launch_blk_step(true, l, buf(q, p), ranks[q].shape, Pb, p, bn,
                                       ranks[q].ctl, bp[q], ranks[q].recv, nranks, ranks[q].log,
-                                      ranks[q].xhist, ranks[q].log_cap, on(q),
-                                      light ? xrow(q) : nullptr,
-                                      light ? (int64_t)SMX_SHARD_HDR : 0);
+                                      ranks[q].xhist, ranks[q].log_cap, on(q));
         }
         for (int q = 0; q < nranks && !err; ++q)
             err = launch_block_sweep(true, buf(q, p), buf(q, p ^ 1), ranks[q].shape, Pb,
@@ -2174,7 +2142,7 @@ int smx_mshard_run(const smx_rank* ranks, int32_t nranks, int32_t parity, int32_
         }
         return 0;
     }
-    return mshard_enqueue(ranks, nranks, parity, k, pivots, exchange);
+    return mshard_enqueue(ranks, nranks, parity, k, pivots);
 }
 
 int smx_mshard_last_error(int32_t* rank_out) {
@@ -2208,8 +2176,8 @@ int smx_mshard_graph_create(const smx_rank* ranks, int32_t nranks, int32_t parit
         for (int q = 1; q < nranks && !lerr; ++q)
             lerr = (int)hipStreamWaitEvent(S(ranks[q].stream), ev[0], 0);
         if (!lerr)
-            lerr = mshard_enqueue(ranks, nranks, parity, k, pivots, SMX_XCHG_COPY, xev.data(),
-                                  ev.data() + nranks, pool_n);
+            lerr = mshard_enqueue(ranks, nranks, parity, k, pivots, xev.data(), ev.data() + nranks,
+                                  pool_n);
         for (int q = 1; q < nranks && !lerr; ++q) {   // join back into ranks[0]'s stream
             lerr = (int)hipEventRecord(ev[(size_t)q], S(ranks[q].stream));
             if (!lerr) lerr = (int)hipStreamWaitEvent(st0, ev[(size_t)q], 0);

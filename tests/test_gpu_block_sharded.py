@@ -97,6 +97,23 @@ def _result(bes):
     return states, logs, tables, full
 
 
+def _one_rank_vs_oracle(T, n, m, k, P, ref, what):
+    """k pivots, P per sweep, on ONE simulated rank that owns every row (full exchange: k_bsh_pack
+    and the sharded k_blk_step) against ref = (oracle table, status, pivots, log): pivot count,
+    log, terminal state and status, and the table by bits (NaN positions equal)."""
+    import special_values as sv
+    Tref, st, done, log = ref
+    bes = _backends(np.array(T), n, m, 1, P)
+    _lockstep(bes, k, P)
+    states, logs, tables, full = _result(bes)
+    assert states[0]["npivots"] == done, (what, states[0])
+    assert np.array_equal(logs[0], log), (what, logs[0].tolist(), log.tolist())
+    assert bool(states[0]["term"]) == (st != 0), (what, states[0])
+    if st != 0:
+        assert states[0]["status"] == st, (what, states[0])
+    sv.same_table_as_oracle(full, Tref, n, m, what)
+
+
 @pytest.mark.parametrize("kind,n,m,world,P,chunks", [
     ("uniform", 1023, 1023, 2, 8, [40, 21]),
     ("uniform", 1001, 777, 3, 5, [60]),

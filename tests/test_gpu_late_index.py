@@ -233,16 +233,31 @@ def test_resident_planted_decisions(knobs, kind, n, m, wg):
 # (pivots per sweep, sweep form, sweep workgroups per CU or 0 for the default grid): every P and
 # every form, forms 7 and 8 with real pairs and quads
 SWEEPS = [(8, 0, 0), (20, 5, 0), (24, 7, 1), (8, 8, 1), (20, 8, 1)]
+# smx_tune_block_planner's settings, and "shard1": the same table, pivots per sweep, sweep form
+# and grid as ONE rank of the row-sharded block chain, the planner every sharded chain runs (the
+# sharded cases below keep a rank within one planner workgroup; here its row pass has winners in
+# late lanes, waves and workgroups)
+PLANS = [0, 2, 1, "shard1"]
+PLAN_IDS = ["wplan", "wstep", "register", "shard1"]
+
+
+def _run_shard1(ref, n, m, k, P, what):
+    from test_gpu_block_sharded import _one_rank_vs_oracle
+    assert ref[1] == m
+    _one_rank_vs_oracle(ref[0], n, m, k, P, ref[2:6], what)
 
 
 def _run_block(knobs, planner, sweep_form, grid, name, plan, P, form, bpc):
     knobs(-1, P)
-    planner(plan, 0)
     sweep_form(form)
     if bpc:
         grid(bpc)
     n, m = li.dims(name)
     ref = li.reference(name, sv.block_k(P))
+    if plan == "shard1":
+        _run_shard1(ref, n, m, sv.block_k(P), P, (name, plan, P, form))
+        return ref
+    planner(plan, 0)
     dev = _device(ref[0], n, m, m)
     assert dev.block_plan()[1] == P
     dev.run(sv.block_k(P))
@@ -252,7 +267,7 @@ def _run_block(knobs, planner, sweep_form, grid, name, plan, P, form, bpc):
 
 
 @pytest.mark.parametrize("P,form,bpc", SWEEPS, ids=["P{}-form{}-bpc{}".format(*s) for s in SWEEPS])
-@pytest.mark.parametrize("plan", [0, 2, 1], ids=["wplan", "wstep", "register"])
+@pytest.mark.parametrize("plan", PLANS, ids=PLAN_IDS)
 @pytest.mark.parametrize("name", ["blk_m", "blk_u", "blk_steep"])
 def test_block_vs_oracle(knobs, planner, sweep_form, grid, name, plan, P, form, bpc):
     """1025 x 1300, a 128 x 128 live block as the tail of the table (rows 897 on, columns 1172
@@ -280,7 +295,7 @@ def test_block_small_window_vs_oracle(knobs, planner, name, plan, nwin):
 
 
 @pytest.mark.parametrize("P,form,bpc", [(24, 7, 1), (20, 8, 1), (8, 5, 0)])
-@pytest.mark.parametrize("plan", [0, 2, 1], ids=["wplan", "wstep", "register"])
+@pytest.mark.parametrize("plan", PLANS, ids=PLAN_IDS)
 def test_block_live_rows_from_an_odd_row(knobs, planner, sweep_form, grid, plan, P, form, bpc):
     """The live block from row 895 (odd, 895 % 4 == 3): its first row closes a row pair and a
     row quad of the table, the rest starts new ones."""
@@ -288,7 +303,7 @@ def test_block_live_rows_from_an_odd_row(knobs, planner, sweep_form, grid, plan,
 
 
 @pytest.mark.parametrize("P,form,bpc", [(8, 0, 0), (20, 5, 0), (24, 8, 1)])
-@pytest.mark.parametrize("plan", [0, 2, 1], ids=["wplan", "wstep", "register"])
+@pytest.mark.parametrize("plan", PLANS, ids=PLAN_IDS)
 def test_block_chain_ends_inside_a_block(knobs, planner, sweep_form, grid, plan, P, form, bpc):
     """A 9 x 9 live block in rows 1015 on: NOT_CONVERGE after 12 pivots -- inside the second
     block of 8, inside the first of 20 and of 24 -- published from the last rows' waves."""
@@ -297,7 +312,7 @@ def test_block_chain_ends_inside_a_block(knobs, planner, sweep_form, grid, plan,
 
 
 @pytest.mark.parametrize("P,form,bpc", [(8, 0, 0), (24, 7, 1), (8, 8, 1)])
-@pytest.mark.parametrize("plan", [0, 2, 1], ids=["wplan", "wstep", "register"])
+@pytest.mark.parametrize("plan", PLANS, ids=PLAN_IDS)
 @pytest.mark.parametrize("kind", ["phase1", "tie"])
 def test_block_planted_decisions(knobs, planner, sweep_form, grid, kind, plan, P, form, bpc):
     """One block of P pivots from every planted phase-1 and tie table at 1025 x 1300: the block's
@@ -306,15 +321,19 @@ def test_block_planted_decisions(knobs, planner, sweep_form, grid, kind, plan, P
     from oracle import c_oracle
     n, m = 1025, 1300
     knobs(-1, P)
-    planner(plan, 0)
     sweep_form(form)
     if bpc:
         grid(bpc)
+    if plan != "shard1":
+        planner(plan, 0)
     dev = None
     for _, at in [c for c in li.planted_cases(n, m) if c[0] == kind]:
         T, flen, want = li.planted(kind, n, m, at)
         Tref, st, done, log = c_oracle.run(T, n, m, flen, P, threads=8)
         assert done >= 1 and tuple(log[0]) == want[1:], (kind, at)
+        if plan == "shard1":
+            _run_shard1((T, flen, Tref, st, done, log), n, m, P, P, (kind, at, plan, P, form))
+            continue
         if dev is None:
             dev = _device(T, n, m, flen)
             assert dev.block_plan()[1] == P
@@ -322,7 +341,8 @@ def test_block_planted_decisions(knobs, planner, sweep_form, grid, kind, plan, P
             dev.upload(T)
         dev.run(P)
         li.same_as_oracle(dev, (T, flen, Tref, st, done, log), n, m, (kind, at, plan, P, form))
-    dev.close()
+    if dev is not None:
+        dev.close()
 
 
 # ----------------------------------------------------------------------------------------------

@@ -145,15 +145,23 @@ def test_resident_overlap_settings_nan_first(knobs, overlap, ovl):
 # ----------------------------------------------------------------------------------------------
 # block pivots
 @pytest.mark.parametrize("P,form", sv.BLOCK)
-@pytest.mark.parametrize("plan", [0, 2, 1], ids=["wplan", "wstep", "register"])
+@pytest.mark.parametrize("plan", [0, 2, 1, "shard1"],
+                         ids=["wplan", "wstep", "register", "shard1"])
 @pytest.mark.parametrize("name", sv.SCENARIOS)
 def test_block_vs_oracle(knobs, planner, sweep_form, name, plan, P, form):
     """Two whole blocks and a ragged one of 3: planner chains and sweep units that leave their
-    fast paths and come back to them."""
+    fast paths and come back to them.  smx_tune_block_planner's settings, and "shard1": the same
+    table, pivots per sweep and sweep form on ONE simulated rank of the row-sharded chain."""
     n, m, _ = sv.CHAIN[0]
     knobs(-1, P)
-    planner(plan, 0)
     sweep_form(form)
+    if plan == "shard1":
+        from test_gpu_block_sharded import _one_rank_vs_oracle
+        k = sv.block_k(P)
+        T, *ref = sv.reference(name, n, m, 5, k)
+        _one_rank_vs_oracle(T, n, m, k, P, ref, (name, n, m, 5, k, "shard1"))
+        return
+    planner(plan, 0)
     dev = _device(name, n, m, 5)
     assert dev.block_plan()[1] == P
     _run_and_compare(dev, name, n, m, 5, sv.block_k(P))
