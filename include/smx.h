@@ -214,6 +214,60 @@ int smx_batch_gm_fits(int32_t Rmax, int32_t ldb);
  * depend on any of them.  Defaults (the measured winners): 1024, 0, 8. */
 int smx_tune_batch_gm(int32_t block, int32_t mirrors, int32_t unroll);
 
+/* ---- selection rules: a dual-simplex rule for warm re-solves --------------------------------
+ * The three batch solves and the host engine take a selection rule.  SMX_RULE_REFERENCE is the
+ * reference's pick_element (simplex.py:70-141), the rule of every call that names none.
+ * SMX_RULE_DUAL is this contract; nothing in the reference computes it.
+ *
+ * A step under SMX_RULE_DUAL on a table T (n, m, flen; row n is the f-row, column m is "-b"):
+ *   1. nb is the smallest i < n with T[i][m] < 0; nf is the smallest j < min(flen, m) with
+ *      T[n][j] < 0 -- the two scans the reference rule makes.
+ *   2. The step is a DUAL STEP iff nb exists, nf does not exist and flen >= m.  Otherwise (primal
+ *      feasible; not dual feasible; a short f-row) it is the reference's step, bit for bit.
+ *   3. In a dual step r = nb.  The candidates are the columns j < m with T[r][j] > 0 (a NaN entry
+ *      is no candidate, as in simplex.py:83).  Each has q_j = T[n][j] / T[r][j]: one IEEE fp64
+ *      division of exactly these two operands, no reciprocal and no fast-division path; every
+ *      operation rounds on its own (no FMA).
+ *   4. The entering column c: among the candidates whose q_j is not NaN the smallest q_j, compared
+ *      with < (so -0.0 and +0.0 tie), a tie to the smaller j; if every candidate's q_j is NaN, the
+ *      smallest such j; if there is no candidate, the status is SMX_INCORRECT (that row proves the
+ *      problem infeasible: the condition of simplex.py:88-89).  This is a strict total order on
+ *      (NaN-ness, q, j), so any reduction tree gives the same winner.
+ *   5. The update is the Jordan step of every other pivot (simplex.py:149-177), unchanged.
+ * Outputs, statuses and layouts are those of the calls without a rule; a run ends at max_pivots
+ * with SMX_PIVOT as ever, degenerate ties included.  The rule adds no synchronisation between
+ * workgroups and no spinning.
+ *
+ * Why a dual step is sound: with e = T[r][c] > 0 and an f-row f >= 0, the new f-row entry of a
+ * column j != c is f[j] - T[r][j] * f[c] / e, which is >= 0 exactly when q_j >= q_c (for
+ * T[r][j] > 0; for T[r][j] <= 0 it is >= 0 anyway), and the new f[c] is f[c] / e >= 0; the
+ * objective entry T[n][m] moves by -T[r][m] * f[c] / e >= 0, so it does not decrease.  A run that
+ * starts dual feasible therefore stays in dual steps until no "-b" is negative, and a table that
+ * is primal and dual feasible is the optimum.  Up to degenerate cycling (f[c] = 0) such a run
+ * terminates; a run that starts with a negative f-row entry takes the reference's steps and
+ * promises no more than they do.
+ *
+ * smx_batch_solve_rule, smx_batch_solve_wg_rule and smx_batch_solve_gm_rule are smx_batch_solve,
+ * smx_batch_solve_wg and smx_batch_solve_gm with `rule` before `stream`: SMX_RULE_REFERENCE
+ * launches the very kernel of the call without a rule, SMX_RULE_DUAL its dual twin (same envelope,
+ * same LDS, same workgroup size; smx_batch_solve_gm_rule honours smx_tune_batch_gm), any other
+ * value returns hipErrorInvalidValue (1) before any HIP call.  Every other refusal and the B == 0
+ * answer are those of the call without a rule. */
+#define SMX_RULE_REFERENCE 0
+#define SMX_RULE_DUAL 1
+int smx_batch_solve_rule(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                         int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                         double* snaps, int32_t* status, int32_t* npivots, int32_t rule,
+                         void* stream);
+int smx_batch_solve_wg_rule(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                            int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                            double* snaps, int32_t* status, int32_t* npivots, int32_t rule,
+                            void* stream);
+int smx_batch_solve_gm_rule(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                            int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                            double* snaps, int32_t* status, int32_t* npivots, int32_t rule,
+                            void* stream);
+
 /* ---- a batch's solutions on the device (one wavefront per LP) ------------------------------
  * After smx_batch_solve, smx_batch_solve_wg or smx_batch_solve_gm: turns every problem's final
  * table (final = their out, fp64 [B][Rmax][ldb]) and pivot log (rc, npivots; max_pivots as in the
@@ -311,9 +365,11 @@ int smx_host_ranging(const double* T, int64_t ld, int32_t n, int32_t m, const in
  * skipped), +0.0 at k >= m: the scenario's own cost vector, on which its objective is formed.
  * Values are formed whatever the base run's status: the table of a capped or failed run is still
  * an equivalent form of its LP.  S is an equivalent form of the perturbed LP under T's labels, so
- * the solve kernels carry on from it as from a fresh problem; the reference's selection rule is no
- * dual simplex, though, and such a warm run need not terminate: a caller reads its
- * status.
+ * the solve kernels carry on from it as from a fresh problem.  Under the default rule, which is no
+ * dual simplex, such a warm run need not terminate.  A table made by constants alone
+ * (dcost all zero) from a base run that ended at SMX_OPTIMUM is dual feasible, and under
+ * SMX_RULE_DUAL (above) the warm run from it terminates, up to degenerate cycling.
+ * Either way a caller caps the run and reads its status.
  *
  * smx_batch_scenario (device pointers, after smx_batch_solution): final fp64 [B][Rmax][ldb], dims
  * int32 [B][3], basis int32 [B][Rmax], nonbasis int32 [B][ldb], func fp64 [B][ldb] (the original
@@ -373,8 +429,11 @@ int smx_batch_solution_from(const double* final, const int32_t* dims, int32_t B,
  * written in the original variables only.  Under identity labels E is the enlarged original
  * problem bit for bit, and E is one bit pattern in any implementation.  E is an equivalent form
  * of the enlarged LP under T's labels and a violated cut shows as a negative "-b", which is what
- * the selection rule's first phase looks for; that rule is no dual simplex, though, and such a
- * warm run need not terminate where a cold solve would: a caller reads its status.
+ * the selection rule's first phase looks for.  Under the default rule, which is no dual simplex,
+ * such a warm run need not terminate where a cold solve would.  E keeps T's f-row, so
+ * after a base run that ended at SMX_OPTIMUM it is dual feasible, and under SMX_RULE_DUAL (above)
+ * the warm run from it terminates, up to degenerate cycling.  Either way a caller
+ * caps the run and reads its status.
  *
  * smx_batch_cuts (device pointers, after smx_batch_solution): final fp64 [B][Rmax][ldb], dims
  * int32 [B][3], basis int32 [B][Rmax], nonbasis int32 [B][ldb], cuts fp64 [B][S][K][ldb] (entry
@@ -735,6 +794,13 @@ int smx_host_select(const double* T, const smx_shape* shape, int32_t* rc_out);
 int smx_host_pivot(const double* Tin, double* Tout, const smx_shape* shape, int32_t r, int32_t c);
 int64_t smx_host_run(double* buf0, double* buf1, const smx_shape* shape, int32_t parity,
                      int64_t k, int32_t* log, int32_t* status_out);
+/* The same two calls under a selection rule (SMX_RULE_* above): with SMX_RULE_REFERENCE they are
+ * smx_host_select and smx_host_run bit for bit, with SMX_RULE_DUAL the host twins of the dual
+ * batch kernels (one candidate order, shared with them).  Any other rule returns -1 and does
+ * nothing.  After SMX_INCORRECT rc_out[0] is the offending row under either rule. */
+int smx_host_select_rule(const double* T, const smx_shape* shape, int32_t rule, int32_t* rc_out);
+int64_t smx_host_run_rule(double* buf0, double* buf1, const smx_shape* shape, int32_t parity,
+                          int64_t k, int32_t rule, int32_t* log, int32_t* status_out);
 
 /* ---- Integer inputs: the first pivot's zero signs (smx_intfirst.hpp) ------------------------
  * The reference holds the caller's Python ints as ints until its first recalculate_matrix

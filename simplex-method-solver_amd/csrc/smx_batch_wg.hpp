@@ -78,6 +78,14 @@ __device__ __forceinline__ bool wg_lp(const int32_t* __restrict__ dims, int B, i
 //            Without it both pointers are unused.
 //   STASH    the ratio test leaves the pivot column it reads in s_pcol on the way, which saves a
 //            second walk down that column of T.
+//   RULE     the selection rule (include/smx.h).  Under SMX_RULE_DUAL a step with a negative "-b"
+//            and no negative f-row entry (nb and nf are reduced together anyway) and flen >= m is
+//            a dual step: one pass over row r in which each thread keeps the best (NaN-ness, q, j)
+//            of its columns, q = f[j] / T[r][j] (the f-row operand from s_frow with MIRRORS), then
+//            the wave reduction, partials in s_c, one barrier and the merge by every wave, as the
+//            ratio test does.  It takes the place of phase 1's first-positive scan; no LDS is
+//            added.  Every other step, and every step under SMX_RULE_REFERENCE, is the code below
+//            unchanged.
 //
 // Between threads: during the update every element is read and written by one thread and every
 // right-hand side comes from s_prow / s_pcol.  What a thread wrote is read by other threads of the
@@ -85,7 +93,7 @@ __device__ __forceinline__ bool wg_lp(const int32_t* __restrict__ dims, int B, i
 // scope; T is a plain pointer (no const __restrict__), so no load is hoisted over a barrier or
 // served from a read-only path.  An LP never spans workgroups: no flags, no spinning, no
 // co-residency.
-template <int U, bool MIRRORS, bool STASH>
+template <int U, bool MIRRORS, bool STASH, int RULE = SMX_RULE_REFERENCE>
 __device__ __forceinline__ void wg_pivot_loop(
     double* T, int ld, double* s_prow, double* s_pcol, double* s_frow, double* s_bcol,
     const WgLp lp, const WgWalk w0, int max_pivots, int32_t* __restrict__ rc,
@@ -139,17 +147,34 @@ __device__ __forceinline__ void wg_pivot_loop(
         if (nb != SMX_NONE) {                                // phase 1 (simplex.py:72-91)
             r = nb;
             const double* rowp = T + r * ld;
-            int p = SMX_NONE;
-            for (int j = tid; j < m; j += nt) {
-                if (rowp[j] > 0.0) {
-                    p = j;
-                    break;
+            if (RULE == SMX_RULE_DUAL && (nf == SMX_NONE && flen >= m)) {   // a dual step
+                Cand bq = cand_none();
+                for (int j = tid; j < m; j += nt) {
+                    const double a = rowp[j];
+                    if (a > 0.0) {
+                        const Cand x = dual_cand((MIRRORS ? s_frow[j] : Tf[j]) / a, j);
+                        bq = cand_sel(dual_better(x, bq), x, bq);
+                    }
                 }
+                bq = wave_dual(bq);
+                if (lane == 0) s_c[wid] = bq;
+                __syncthreads();
+                bq = cand_none();
+                if (lane < nw) bq = s_c[lane];
+                c = wave_dual(bq).idx;
+            } else {
+                int p = SMX_NONE;
+                for (int j = tid; j < m; j += nt) {
+                    if (rowp[j] > 0.0) {
+                        p = j;
+                        break;
+                    }
+                }
+                p = wave_min_int(p);
+                if (lane == 0) s_p1[wid] = p;
+                __syncthreads();
+                c = wg_merge_min(s_p1, nw, lane);
             }
-            p = wave_min_int(p);
-            if (lane == 0) s_p1[wid] = p;
-            __syncthreads();
-            c = wg_merge_min(s_p1, nw, lane);
             if (c == SMX_NONE) {
                 status = SMX_INCORRECT;
                 break;
@@ -306,6 +331,35 @@ __global__ __launch_bounds__(kWgMaxBlock) void k_batch_wg(
                                    rc + 2 * hs, xv + 2 * hs,
                                    snaps ? snaps + hs * tab_elems : nullptr, ldb, tab_elems,
                                    status_out + b, np_out + b);
+    double* dst = out + (size_t)b * tab_elems;
+    for (WgWalk w = w0; w.i < R; w.next()) dst[w.i * ldb + w.j] = s_T[w.i * ldl + w.j];
+}
+
+// k_batch_wg_dual: k_batch_wg under SMX_RULE_DUAL -- the same arguments, LDS and envelope; only
+// wg_pivot_loop's rule differs.  (k_batch_wg keeps its own text: through a shared wrapper its
+// instruction stream changes.)
+__global__ __launch_bounds__(kWgMaxBlock) void k_batch_wg_dual(
+    const double* __restrict__ tabs, const int32_t* __restrict__ dims, int B, int Rmax, int ldb,
+    int ldl, int max_pivots, double* __restrict__ out, int32_t* __restrict__ rc,
+    double* __restrict__ xv, double* __restrict__ snaps, int32_t* __restrict__ status_out,
+    int32_t* __restrict__ np_out) {
+    extern __shared__ double s_wg[];   // s_T[Rmax * ldl], s_prow[ldb], s_pcol[Rmax]
+    double* s_T = s_wg;
+    double* s_prow = s_T + (size_t)Rmax * ldl;
+    double* s_pcol = s_prow + ldb;
+    WgLp lp;
+    if (!wg_lp(dims, B, Rmax, ldb, status_out, np_out, lp)) return;
+    const int b = blockIdx.x;
+    const int R = lp.n + 1;
+    const size_t tab_elems = (size_t)Rmax * ldb;
+    const size_t hs = (size_t)b * max_pivots;
+    const WgWalk w0(threadIdx.x, blockDim.x, lp.m + 1);
+    const double* src = tabs + (size_t)b * tab_elems;
+    for (WgWalk w = w0; w.i < R; w.next()) s_T[w.i * ldl + w.j] = src[w.i * ldb + w.j];
+    __syncthreads();
+    wg_pivot_loop<1, false, false, SMX_RULE_DUAL>(
+        s_T, ldl, s_prow, s_pcol, nullptr, nullptr, lp, w0, max_pivots, rc + 2 * hs, xv + 2 * hs,
+        snaps ? snaps + hs * tab_elems : nullptr, ldb, tab_elems, status_out + b, np_out + b);
     double* dst = out + (size_t)b * tab_elems;
     for (WgWalk w = w0; w.i < R; w.next()) dst[w.i * ldb + w.j] = s_T[w.i * ldl + w.j];
 }

@@ -93,6 +93,35 @@ __device__ __forceinline__ First wave_first(First a) {
     return a;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Entering-column order of a dual step (SMX_RULE_DUAL, include/smx.h): candidates whose ratio q
+// is not NaN come first, among them the smaller q (compared with <, so -0.0 and +0.0 tie), a tie
+// to the smaller column; NaN ratios by column.  A strict total order on (NaN-ness, q, column), so
+// any reduction tree gives the same winner.  Shared by the host engine and the batch kernels,
+// which carry a candidate as a Cand with cls = 0 (q not NaN), 1 (q NaN) or 3 (none).
+__host__ __device__ inline bool dual_before(int an, double aq, int aj, int bn, double bq, int bj) {
+    const bool cq = (aq < bq) | ((aq == bq) & (aj < bj));
+    const bool cj = aj < bj;
+    return (an < bn) | ((an == bn) & (an == 0 ? cq : cj));
+}
+
+__device__ __forceinline__ Cand dual_cand(double q, int j) {
+    return Cand{isnan(q) ? 1 : 0, j, q};
+}
+
+__device__ __forceinline__ bool dual_better(const Cand& a, const Cand& b) {
+    return dual_before(a.cls, a.v, a.idx, b.cls, b.v, b.idx);
+}
+
+__device__ __forceinline__ Cand wave_dual(Cand a) {
+#pragma unroll
+    for (int mask = 32; mask >= 1; mask >>= 1) {
+        Cand o = shfl_xor_cand(a, mask);
+        a = cand_sel(dual_better(o, a), o, a);
+    }
+    return a;
+}
+
 // The same three reductions through DPP instead of LDS-crossbar shuffles (the planner's per-step
 // decision and record merge, smx_block.hpp): lane pairs within quads (quad_perm), then the
 // half-row and row mirrors (lane i <-> 7 - i, 15 - i) leave every lane of a 16-lane row holding

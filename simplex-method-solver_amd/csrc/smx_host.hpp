@@ -82,6 +82,40 @@ int host_select(const double* T, int64_t ld, int n, int m, int flen, int* r_out,
     return SMX_PIVOT;
 }
 
+// pick_element under a selection rule (include/smx.h): a dual step where SMX_RULE_DUAL asks for
+// one, with the kernels' candidate order (dual_before), else host_select.
+int host_select_rule(const double* T, int64_t ld, int n, int m, int flen, int rule, int* r_out,
+                     int* c_out) {
+    if (rule == SMX_RULE_DUAL && flen >= m) {
+        int nb = SMX_NONE;
+        for (int i = 0; i < n && nb == SMX_NONE; ++i)
+            if (T[(int64_t)i * ld + m] < 0.0) nb = i;
+        const double* f = T + (int64_t)n * ld;
+        bool nf = false;
+        for (int j = 0; j < m && !nf; ++j) nf = f[j] < 0.0;
+        if (nb != SMX_NONE && !nf) {
+            const double* row = T + (int64_t)nb * ld;
+            int bn = 3, bj = SMX_NONE;
+            double bq = 0.0;
+            for (int j = 0; j < m; ++j) {
+                if (row[j] > 0.0) {
+                    const double q = f[j] / row[j];
+                    const int qn = __builtin_isnan(q) ? 1 : 0;
+                    if (dual_before(qn, q, j, bn, bq, bj)) {
+                        bn = qn;
+                        bq = q;
+                        bj = j;
+                    }
+                }
+            }
+            *r_out = nb;
+            *c_out = bj;
+            return bj == SMX_NONE ? SMX_INCORRECT : SMX_PIVOT;
+        }
+    }
+    return host_select(T, ld, n, m, flen, r_out, c_out);
+}
+
 // recalculate_matrix (simplex.py:149-177), out of place: every element of rows 0..n, columns
 // 0..C-1 of Tout from Tin.
 void host_pivot(const double* Tin, double* Tout, int64_t ld, int R, int C, int r, int c) {
@@ -119,15 +153,25 @@ int smx_host_pivot(const double* Tin, double* Tout, const smx_shape* s, int32_t 
     return 0;
 }
 
-int64_t smx_host_run(double* buf0, double* buf1, const smx_shape* s, int32_t parity, int64_t k,
-                     int32_t* log, int32_t* status_out) {
+int smx_host_select_rule(const double* T, const smx_shape* s, int32_t rule, int32_t* rc_out) {
+    if (rule != SMX_RULE_REFERENCE && rule != SMX_RULE_DUAL) return -1;
+    int r, c;
+    const int st = host_select_rule(T, s->ld, s->n, s->m, s->flen, rule, &r, &c);
+    rc_out[0] = r;
+    rc_out[1] = c;
+    return st;
+}
+
+int64_t smx_host_run_rule(double* buf0, double* buf1, const smx_shape* s, int32_t parity,
+                          int64_t k, int32_t rule, int32_t* log, int32_t* status_out) {
+    if (rule != SMX_RULE_REFERENCE && rule != SMX_RULE_DUAL) return -1;
     double* buf[2] = {buf0, buf1};
     int64_t done = 0;
     int st = SMX_PIVOT;
     while (done < k) {
         int r, c;
         const double* T = buf[(parity + done) & 1];
-        st = host_select(T, s->ld, s->n, s->m, s->flen, &r, &c);
+        st = host_select_rule(T, s->ld, s->n, s->m, s->flen, rule, &r, &c);
         if (st != SMX_PIVOT) break;
         if (s->flen > s->m + 1 || (s->flen < s->m && c >= s->flen)) {
             st = SMX_FSHORT;   // the reference indexes the f-row out of range (simplex.py:159-175)
@@ -142,6 +186,11 @@ int64_t smx_host_run(double* buf0, double* buf1, const smx_shape* s, int32_t par
     }
     *status_out = (done == k && st == SMX_PIVOT) ? SMX_IDLE : st;
     return done;
+}
+
+int64_t smx_host_run(double* buf0, double* buf1, const smx_shape* s, int32_t parity, int64_t k,
+                     int32_t* log, int32_t* status_out) {
+    return smx_host_run_rule(buf0, buf1, s, parity, k, SMX_RULE_REFERENCE, log, status_out);
 }
 
 }  // extern "C"

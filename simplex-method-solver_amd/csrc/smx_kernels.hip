@@ -1170,6 +1170,27 @@ int smx_batch_solve(const double* tabs, const int32_t* dims, int32_t B, int32_t 
     return (int)hipGetLastError();
 }
 
+int smx_batch_solve_rule(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                         int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                         double* snaps, int32_t* status, int32_t* npivots, int32_t rule,
+                         void* stream) {
+    if (rule == SMX_RULE_REFERENCE)
+        return smx_batch_solve(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv, snaps, status,
+                               npivots, stream);
+    if (rule != SMX_RULE_DUAL) return (int)hipErrorInvalidValue;
+    if (B < 0 || Rmax < 1 || Rmax > kWave || ldb < 1 || ldb > 64 || max_pivots < 0)
+        return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    using BatchFn = void (*)(const double*, const int32_t*, int, int, int, int, double*, int32_t*,
+                             double*, double*, int32_t*, int32_t*);
+    const BatchFn fn = ldb <= 4 ? k_batch_dual<4> : ldb <= 8 ? k_batch_dual<8>
+                       : ldb <= 16 ? k_batch_dual<16> : ldb <= 32 ? k_batch_dual<32>
+                                                                  : k_batch_dual<64>;
+    hipLaunchKernelGGL(fn, dim3((B + 3) / 4), dim3(256), 0, S(stream), tabs, dims, B, Rmax, ldb,
+                       max_pivots, out, rc, xv, snaps, status, npivots);
+    return (int)hipGetLastError();
+}
+
 // ---- batched mid-sized LPs (smx_batch_wg.hpp) ------------------------------------------------
 // The envelope: the table at an odd row pitch, the old pivot row and the old pivot column in
 // dynamic LDS, within a CU's 160 KiB less the kernel's static part (the reduction partials,
@@ -1213,6 +1234,24 @@ int smx_batch_solve_wg(const double* tabs, const int32_t* dims, int32_t B, int32
     if (B == 0) return 0;
     if (const int err = wg_raise_lds_limit<k_batch_wg>((int)kWgLdsMax)) return err;
     hipLaunchKernelGGL(k_batch_wg, dim3(B), dim3(wg_block(Rmax, ldb)), (size_t)lds, S(stream),
+                       tabs, dims, B, Rmax, ldb, (int)wg_ldl(ldb), max_pivots, out, rc, xv, snaps,
+                       status, npivots);
+    return (int)hipGetLastError();
+}
+
+int smx_batch_solve_wg_rule(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                            int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                            double* snaps, int32_t* status, int32_t* npivots, int32_t rule,
+                            void* stream) {
+    if (rule == SMX_RULE_REFERENCE)
+        return smx_batch_solve_wg(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv, snaps, status,
+                                  npivots, stream);
+    if (rule != SMX_RULE_DUAL) return (int)hipErrorInvalidValue;
+    const int64_t lds = wg_lds_bytes(Rmax, ldb);
+    if (!wg_args_ok(B, max_pivots) || lds < 0) return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    if (const int err = wg_raise_lds_limit<k_batch_wg_dual>((int)kWgLdsMax)) return err;
+    hipLaunchKernelGGL(k_batch_wg_dual, dim3(B), dim3(wg_block(Rmax, ldb)), (size_t)lds, S(stream),
                        tabs, dims, B, Rmax, ldb, (int)wg_ldl(ldb), max_pivots, out, rc, xv, snaps,
                        status, npivots);
     return (int)hipGetLastError();
@@ -1262,6 +1301,28 @@ int smx_batch_solve_gm(const double* tabs, const int32_t* dims, int32_t B, int32
     else
         launch = g_gm_unroll == 8 ? launch_batch_gm<false, 8>
                  : g_gm_unroll == 4 ? launch_batch_gm<false, 4> : launch_batch_gm<false, 1>;
+    return launch(g_gm_block, (int)(16 * kGmMaxSum), tabs, dims, B, Rmax, ldb, max_pivots, out, rc,
+                  xv, snaps, status, npivots, S(stream));
+}
+
+int smx_batch_solve_gm_rule(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                            int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                            double* snaps, int32_t* status, int32_t* npivots, int32_t rule,
+                            void* stream) {
+    if (rule == SMX_RULE_REFERENCE)
+        return smx_batch_solve_gm(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv, snaps, status,
+                                  npivots, stream);
+    if (rule != SMX_RULE_DUAL) return (int)hipErrorInvalidValue;
+    if (!wg_args_ok(B, max_pivots) || !gm_fits(Rmax, ldb)) return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    GmLaunch* launch;
+    if (g_gm_mirrors)
+        launch = g_gm_unroll == 8 ? launch_batch_gm_dual<true, 8>
+                 : g_gm_unroll == 4 ? launch_batch_gm_dual<true, 4> : launch_batch_gm_dual<true, 1>;
+    else
+        launch = g_gm_unroll == 8 ? launch_batch_gm_dual<false, 8>
+                 : g_gm_unroll == 4 ? launch_batch_gm_dual<false, 4>
+                                    : launch_batch_gm_dual<false, 1>;
     return launch(g_gm_block, (int)(16 * kGmMaxSum), tabs, dims, B, Rmax, ldb, max_pivots, out, rc,
                   xv, snaps, status, npivots, S(stream));
 }

@@ -20,6 +20,18 @@ LIB_PATH = os.path.join(HERE, os.path.basename(os.environ.get("SMX_LIB", "libsmx
 # outcome codes, include/smx.h
 PIVOT, OPTIMUM, INCORRECT, NOT_CONVERGE, FSHORT, IDLE = 0, 1, 2, 3, 4, 5
 NONE = 0x7F7F7F7F
+# selection rules, include/smx.h
+RULE_REFERENCE, RULE_DUAL = 0, 1
+RULES = {"reference": RULE_REFERENCE, "dual": RULE_DUAL}
+
+
+def rule_code(rule) -> int:
+    """The SMX_RULE_* code of a rule's name; ValueError for anything else."""
+    if not isinstance(rule, str) or rule not in RULES:
+        raise ValueError(f"rule must be one of {tuple(RULES)}, not {rule!r}")
+    return RULES[rule]
+
+
 SHARD_HDR = 8
 CTL_BYTES = 128
 PART_BYTES = 32
@@ -106,6 +118,7 @@ EXPORTS = (
     "smx_set_xpos", "smx_reset", "smx_select", "smx_finalize", "smx_update",
     "smx_run", "smx_run_timed", "smx_graph_create", "smx_graph_launch", "smx_graph_destroy", "smx_update_forced",
     "smx_batch_solve", "smx_batch_solve_wg", "smx_batch_wg_lds_bytes", "smx_batch_solve_gm", "smx_batch_gm_fits", "smx_tune_batch_gm",
+    "smx_batch_solve_rule", "smx_batch_solve_wg_rule", "smx_batch_solve_gm_rule",
     "smx_batch_solution", "smx_batch_solution_lds_bytes",
     "smx_batch_ranging", "smx_batch_ranging_fits", "smx_host_ranging",
     "smx_batch_scenario", "smx_batch_scenario_fits", "smx_host_scenario", "smx_batch_solution_from",
@@ -123,7 +136,7 @@ EXPORTS = (
     "smx_bshard_prime",
     "smx_bshard_pack", "smx_bshard_step", "smx_bshard_sweep", "smx_bshard_publish",
     "smx_bshard_pick", "smx_bshard_step_light", "smx_tune_shard_xchg",
-    "smx_host_select", "smx_host_pivot", "smx_host_run", "smx_timer_reserve",
+    "smx_host_select", "smx_host_pivot", "smx_host_run", "smx_host_select_rule", "smx_host_run_rule", "smx_timer_reserve",
     "smx_mshard_comms", "smx_mshard_run", "smx_int_first_fix", "smx_host_int_first_fix",
     "smx_diag_path_counts", "smx_comm_info", "smx_mshard_graph_create", "smx_mshard_last_error",
 )
@@ -186,6 +199,12 @@ def load():
                                ctypes.c_int),
         "smx_batch_gm_fits": ([i32, i32], ctypes.c_int),
         "smx_tune_batch_gm": ([i32, i32, i32], ctypes.c_int),
+        "smx_batch_solve_rule": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp],
+                                 ctypes.c_int),
+        "smx_batch_solve_wg_rule": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp],
+                                    ctypes.c_int),
+        "smx_batch_solve_gm_rule": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp],
+                                    ctypes.c_int),
         "smx_batch_solution": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
                                ctypes.c_int),
         "smx_batch_solution_lds_bytes": ([i32, i32], ctypes.c_int64),
@@ -259,6 +278,8 @@ def load():
         "smx_host_select": ([vp, sp, vp], ctypes.c_int),
         "smx_host_pivot": ([vp, vp, sp, i32, i32], ctypes.c_int),
         "smx_host_run": ([vp, vp, sp, i32, i64, vp, vp], ctypes.c_int64),
+        "smx_host_select_rule": ([vp, sp, i32, vp], ctypes.c_int),
+        "smx_host_run_rule": ([vp, vp, sp, i32, i64, i32, vp, vp], ctypes.c_int64),
         "smx_timer_reserve": ([i32], ctypes.c_int),
         "smx_mshard_comms": ([ctypes.POINTER(ctypes.c_void_p), i32, ctypes.POINTER(i32)],
                              ctypes.c_int),

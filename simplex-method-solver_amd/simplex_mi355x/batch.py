@@ -27,14 +27,19 @@ each cost can move before that final basis changes, formed on the device by ``k_
 move: what is the optimum now?" without solving the perturbed problems from scratch:
 ``k_batch_scenario`` (csrc/smx_scenario.hpp) re-expresses every scenario under its LP's final
 basis on the device, and the same solve kernel carries on from that table -- a handful of pivots
-where a cold solve takes hundreds.  Such a warm run need not terminate: every
-scenario reports its status, and the object-level call falls back to a cold solve.
+where a cold solve takes hundreds.  Under the default selection rule such a warm run need not
+terminate: every scenario reports its status, and the object-level call falls back to
+a cold solve.  ``warm_rule="dual"`` runs the warm solve under the dual-simplex rule of
+include/smx.h (SMX_RULE_DUAL): from a dual-feasible table -- constants moved, costs
+not, after a base run that ended at an optimum -- it terminates, up to degenerate cycling; status
+and cap remain.
 
 ``solve_batch_cuts`` (and ``solve_batch_cuts_arrays``) answer "I have new constraints: what is the
 optimum now?" in the same way: ``k_batch_cuts`` (csrc/smx_cuts.hpp) writes every cut, given in the
 original variables, as one more row under its LP's final basis, and the solve kernel that takes
-the enlarged block carries on from there.  The same caveat holds and the same cold
-fallback answers it.
+the enlarged block carries on from there.  The same caveat holds under the default
+rule and the same cold fallback answers it; an extended table keeps its base run's f-row, so after
+an optimum ``warm_rule="dual"`` applies to every cut set.
 
 The host side of all this is stated once.  Array level: ``_launch_arrays`` and
 ``_launch_tier`` check a launch, ``_device_solve`` / ``_device_solution`` / ``_device_ranging``
@@ -238,10 +243,11 @@ _SOLVERS = {"wave": "smx_batch_solve", "workgroup": "smx_batch_solve_wg",
             "global": "smx_batch_solve_gm"}
 
 
-def _device_solve(L, stream, tier, d_tabs, d_dims, cap, history=False):
+def _device_solve(L, stream, tier, d_tabs, d_dims, cap, history=False, rule=_lib.RULE_REFERENCE):
     """Enqueue the solve kernel of ``tier`` on fresh outputs, capped at ``cap`` pivots; returns
     the device tensors (final, rc, xv, status, npivots, snaps), ``snaps`` None without
-    ``history``."""
+    ``history``.  ``rule`` (an SMX_RULE_* code): the reference rule goes through the entry point
+    without a rule, any other through the tier's ``_rule`` entry."""
     count, rows, ldb = d_tabs.shape
     dev = d_tabs.device
     d_out = torch.empty_like(d_tabs)
@@ -252,10 +258,14 @@ def _device_solve(L, stream, tier, d_tabs, d_dims, cap, history=False):
     d_st = torch.zeros(count, dtype=torch.int32, device=dev)
     d_np = torch.zeros(count, dtype=torch.int32, device=dev)
     what = _SOLVERS[tier]
-    _lib.check(getattr(L, what)(
-        d_tabs.data_ptr(), d_dims.data_ptr(), count, rows, ldb, cap, d_out.data_ptr(),
-        d_rc.data_ptr(), d_xv.data_ptr(), d_snaps.data_ptr() if history else None,
-        d_st.data_ptr(), d_np.data_ptr(), stream.cuda_stream), what)
+    args = (d_tabs.data_ptr(), d_dims.data_ptr(), count, rows, ldb, cap, d_out.data_ptr(),
+            d_rc.data_ptr(), d_xv.data_ptr(), d_snaps.data_ptr() if history else None,
+            d_st.data_ptr(), d_np.data_ptr())
+    if rule == _lib.RULE_REFERENCE:
+        _lib.check(getattr(L, what)(*args, stream.cuda_stream), what)
+    else:
+        what += "_rule"
+        _lib.check(getattr(L, what)(*args, int(rule), stream.cuda_stream), what)
     return d_out, d_rc, d_xv, d_st, d_np, d_snaps
 
 
@@ -313,12 +323,12 @@ def _ranging_arrays(rng, lead):
 
 
 def _enqueue_base(L, stream, tier, d_tabs, d_dims, P, history=False, solution=True,
-                  ranging=False):
+                  ranging=False, rule=_lib.RULE_REFERENCE):
     """Enqueue a launch's solve on ``tier`` and, as asked, its solution and its ranges; returns
     (the ``_device_solve`` tensors, the original objective rows, the ``_device_solution`` tensors,
     the ``_device_ranging`` tensors), None for what was not asked.  Nothing comes back yet:
     ``_base_arrays`` does that."""
-    run = _device_solve(L, stream, tier, d_tabs, d_dims, P, history)
+    run = _device_solve(L, stream, tier, d_tabs, d_dims, P, history, rule)
     d_func = sol = rng = None
     if solution:
         # the original objective rows (row n_k of problem k), gathered on the device
@@ -350,7 +360,7 @@ def _base_arrays(run, sol, rng, tables=False):
 def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256,
                        history: bool = False, device=None, kernel: str = "auto",
                        solution: bool = False, tables: bool = True,
-                       ranging: bool = False) -> dict:
+                       ranging: bool = False, rule: str = "reference") -> dict:
     """Array-level batch solve (no Python objects per problem).
 
     ``tabs``: float64 [B][Rmax][ldb], problem k in rows 0..n_k (f-row = row n_k), columns
@@ -378,7 +388,14 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
     ``tables``) adds what ``k_batch_ranging`` makes of every final table and those labels on the
     device: ``rhs_lo``, ``rhs_hi`` [B][Rmax - 1] and ``cost_lo``, ``cost_hi`` [B][ldb - 1] (+0.0
     past n_k / m_k); see ``Ranging``.
+
+    ``rule``: ``"reference"`` (the default: the reference's pick_element) or ``"dual"``
+    (SMX_RULE_DUAL of include/smx.h: a step from a table with a negative constant and no negative
+    cost is a dual-simplex step, every other step the reference's).  Any other value raises
+    ValueError before the device is asked for.  The result's keys, shapes and dtypes do not depend
+    on it.
     """
+    code = _lib.rule_code(rule)
     if not tables and not solution:
         raise ValueError("tables=False needs solution=True: nothing else would report the answer")
     if ranging and not solution:
@@ -398,7 +415,7 @@ def solve_batch_arrays(tabs: np.ndarray, dims: np.ndarray, max_pivots: int = 256
         d_dims = torch.from_numpy(dims).to(dev)
         run, _, sol, rng = _enqueue_base(_lib.load(), torch.cuda.current_stream(dev), which,
                                          d_tabs, d_dims, int(max_pivots), history, solution,
-                                         ranging)
+                                         ranging, code)
         return _base_arrays(run, sol, rng, tables)
 
 
@@ -517,22 +534,22 @@ def _solution_at(arrays, index, n, m):
                     arrays["nonbasis"][index][:m].copy(), int(arrays["npivots"][index]))
 
 
-def _fallback(cons, func, max_pivots, history):
+def _fallback(cons, func, max_pivots, history, rule="reference"):
     try:
         sm = SimplexMethod(cons, func)
         if history:
-            return sm.get_solution(max_pivots=max_pivots), sm.status
-        return sm.solve(record_history=False, max_pivots=max_pivots), sm.status
+            return sm.get_solution(max_pivots=max_pivots, rule=rule), sm.status
+        return sm.solve(record_history=False, max_pivots=max_pivots, rule=rule), sm.status
     except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
         return exc, "exception"
 
 
-def _fallback_answer(cons, func, max_pivots, answer):
+def _fallback_answer(cons, func, max_pivots, answer, rule="reference"):
     """One problem through ``SimplexMethod``; ``answer`` is the method that reads the result off
     the solved object (``SimplexMethod.solution`` / ``.ranging``)."""
     try:
         sm = SimplexMethod(cons, func)
-        sm.solve(record_history=False, max_pivots=max_pivots)
+        sm.solve(record_history=False, max_pivots=max_pivots, rule=rule)
         return answer(sm), sm.status
     except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
         return exc, "exception"
@@ -556,7 +573,7 @@ def _drive(problems, kernel, max_pivots, history, single, launch):
 
 
 def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=None,
-                kernel: str = "auto"):
+                kernel: str = "auto", rule: str = "reference"):
     """Solve every ``(constraints, function)``; returns ``(results, statuses)``.
 
     ``results[k]`` is the ``get_solution()`` list of problem k (``history=False``: only the
@@ -571,17 +588,20 @@ def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=No
     ``kernel="workgroup"`` sends the wave problems through the workgroup kernel too;
     ``kernel="wave"`` raises ValueError if a problem needs the workgroup kernel; both leave the
     global problems to ``SimplexMethod``.  ``kernel="global"`` sends the wave and workgroup
-    problems through the global-memory kernel too, whatever their number."""
+    problems through the global-memory kernel too, whatever their number.
+    ``rule`` is the selection rule of every solve, as in ``solve_batch_arrays`` (the problems sent
+    through ``SimplexMethod`` included); an unknown one raises ValueError first."""
+    _lib.rule_code(rule)
     problems = list(problems)
     results = [None] * len(problems)
     statuses = [None] * len(problems)
     P = int(max_pivots)
 
     def single(k, c, f):
-        results[k], statuses[k] = _fallback(c, f, max_pivots, history)
+        results[k], statuses[k] = _fallback(c, f, max_pivots, history, rule)
 
     def launch(which, idx, tabs, dims):
-        out = solve_batch_arrays(tabs, dims, max_pivots, history, device, kernel=which)
+        out = solve_batch_arrays(tabs, dims, max_pivots, history, device, kernel=which, rule=rule)
         # Hundreds of thousands of fresh, acyclic lists: pause the cyclic collector while they
         # are built, or its generational passes rescan the growing result set (5x slower at 20k
         # LPs).
@@ -601,20 +621,22 @@ def solve_batch(problems, max_pivots: int = 256, history: bool = True, device=No
     return results, statuses
 
 
-def _solve_batch_answers(problems, max_pivots, device, kernel, answer, ranging, at):
+def _solve_batch_answers(problems, max_pivots, device, kernel, answer, ranging, at,
+                         rule="reference"):
     """``solve_batch_solutions`` and ``solve_batch_ranges``: ``answer`` reads a fallback's result
     off its ``SimplexMethod``, ``at(arrays, q, n, m)`` a launch member's off the arrays."""
+    _lib.rule_code(rule)
     problems = list(problems)
     results = [None] * len(problems)
     statuses = [None] * len(problems)
     P = int(max_pivots)
 
     def single(k, c, f):
-        results[k], statuses[k] = _fallback_answer(c, f, max_pivots, answer)
+        results[k], statuses[k] = _fallback_answer(c, f, max_pivots, answer, rule)
 
     def launch(which, idx, tabs, dims):
         out = solve_batch_arrays(tabs, dims, max_pivots, False, device, kernel=which,
-                                 solution=True, tables=False, ranging=ranging)
+                                 solution=True, tables=False, ranging=ranging, rule=rule)
         for q, k in enumerate(idx):
             results[k] = at(out, q, int(dims[q, 0]), int(dims[q, 1]))
             statuses[k] = _status_name(int(out["status"][q]), int(out["npivots"][q]), P)
@@ -623,7 +645,8 @@ def _solve_batch_answers(problems, max_pivots, device, kernel, answer, ranging, 
     return results, statuses
 
 
-def solve_batch_solutions(problems, max_pivots: int = 256, device=None, kernel: str = "auto"):
+def solve_batch_solutions(problems, max_pivots: int = 256, device=None, kernel: str = "auto",
+                          rule: str = "reference"):
     """Solve every ``(constraints, function)`` for its whole answer; returns
     ``(solutions, statuses)``.
 
@@ -633,9 +656,9 @@ def solve_batch_solutions(problems, max_pivots: int = 256, device=None, kernel: 
     the reference would raise; ``statuses[k]`` as in ``solve_batch``.  The values stand whatever
     the status.  Routing and launch splitting are ``solve_batch``'s; of a launch only the
     solutions come back from the device (``solve_batch_arrays(solution=True, tables=False)``),
-    and no ``Info`` objects are built."""
+    and no ``Info`` objects are built.  ``rule`` as in ``solve_batch``."""
     return _solve_batch_answers(problems, max_pivots, device, kernel, SimplexMethod.solution,
-                                False, _solution_at)
+                                False, _solution_at, rule)
 
 
 def _ranging_at(arrays, q, n, m):
@@ -643,7 +666,8 @@ def _ranging_at(arrays, q, n, m):
                    arrays["cost_lo"][q, :m].copy(), arrays["cost_hi"][q, :m].copy())
 
 
-def solve_batch_ranges(problems, max_pivots: int = 256, device=None, kernel: str = "auto"):
+def solve_batch_ranges(problems, max_pivots: int = 256, device=None, kernel: str = "auto",
+                       rule: str = "reference"):
     """Solve every ``(constraints, function)`` for the ranges of its final basis; returns
     ``(ranges, statuses)``.
 
@@ -652,19 +676,22 @@ def solve_batch_ranges(problems, max_pivots: int = 256, device=None, kernel: str
     ``solve(record_history=False)``, or the ``IndexError`` the reference would raise;
     ``statuses[k]`` as in ``solve_batch``.  The values stand whatever the status.  Routing and
     launch splitting are ``solve_batch``'s; of a launch only the solutions and the ranges come
-    back from the device (``solve_batch_arrays(solution=True, ranging=True, tables=False)``)."""
+    back from the device (``solve_batch_arrays(solution=True, ranging=True, tables=False)``).
+    ``rule`` as in ``solve_batch``."""
     return _solve_batch_answers(problems, max_pivots, device, kernel, SimplexMethod.ranging,
-                                True, _ranging_at)
+                                True, _ranging_at, rule)
 
 
-def _warm_chain(L, dev, tabs, dims, tier, P, S, make, rows, warm_tier, Pw, ranging, log):
+def _warm_chain(L, dev, tabs, dims, tier, P, S, make, rows, warm_tier, Pw, ranging, log,
+                warm_rule=_lib.RULE_REFERENCE):
     """The chain of both warm calls, on one stream and with no host round trip between the steps:
     the base launch of ``tabs`` / ``dims`` on ``tier`` (``_enqueue_base``), then for every slice of
     the S sets ``make(stream, s0, c, final, d_dims, func, basis, nonbasis)``, which enqueues the
     kernel that writes the B * c warm tables of sets s0..s0 + c - 1 (``rows`` rows each) from the
     base launch's device tensors and returns (tables, their dims, their function rows, the
-    ``start`` of ``_device_solution``); the warm solve on ``warm_tier`` capped at ``Pw``, its
-    solution from ``start`` and, with ``ranging``, its ranges.  A slice holds as many sets as keep
+    ``start`` of ``_device_solution``); the warm solve on ``warm_tier`` capped at ``Pw`` under
+    the selection rule ``warm_rule`` (the base launch keeps the reference rule), its solution from
+    ``start`` and, with ``ranging``, its ranges.  A slice holds as many sets as keep
     its tables under ``GM_TABLE_BUDGET``.  Only when everything is enqueued does anything come
     back: ``base`` (``_base_arrays``) and per set, shaped [B][S]..., ``status``, ``npivots``, with
     ``log`` the warm pivot log ``rc``, the solution arrays and with ``ranging`` the range arrays.
@@ -683,7 +710,7 @@ def _warm_chain(L, dev, tabs, dims, tier, P, S, make, rows, warm_tier, Pw, rangi
             d_wtabs, d_wdims, d_wfunc, start = make(stream, s0, c, run[0], d_dims, d_func,
                                                     sol[3], sol[4])
             d_wout, d_wrc, _, d_wst, d_wnp, _ = _device_solve(L, stream, warm_tier, d_wtabs,
-                                                              d_wdims, Pw)
+                                                              d_wdims, Pw, rule=warm_rule)
             wsol = _device_solution(L, stream, d_wout, d_wdims, Pw, d_wrc, d_wnp, d_wfunc, start)
             wrng = _device_ranging(L, stream, d_wout, d_wdims, wsol[3], wsol[4]) if ranging else ()
             slices.append((c, d_wst, d_wnp, d_wrc if log else None, wsol, wrng))
@@ -707,7 +734,8 @@ def _warm_chain(L, dev, tabs, dims, tier, P, S, make, rows, warm_tier, Pw, rangi
 
 def solve_batch_scenarios_arrays(tabs: np.ndarray, dims: np.ndarray, drhs: np.ndarray,
                                  dcost: np.ndarray, max_pivots: int = 256, warm_pivots=None,
-                                 device=None, kernel: str = "auto", ranging: bool = False) -> dict:
+                                 device=None, kernel: str = "auto", ranging: bool = False,
+                                 warm_rule: str = "reference") -> dict:
     """Array-level what-if solve: every LP of ``tabs`` / ``dims`` (as in ``solve_batch_arrays``)
     and S scenarios of each.  ``drhs``: float64 [B][S][Rmax - 1], ``drhs[k, s, i]`` is added to
     the constant of constraint i of problem k; ``dcost``: float64 [B][S][ldb - 1], added to its
@@ -724,10 +752,18 @@ def solve_batch_scenarios_arrays(tabs: np.ndarray, dims: np.ndarray, drhs: np.nd
     Returns ``base``: exactly the dict of ``solve_batch_arrays(solution=True, tables=False,
     ranging=ranging)``; and per scenario, shaped [B][S]...: ``status``, ``npivots`` (the warm
     pivots only), ``x``, ``duals``, ``objective`` (on the scenario's own costs), ``basis``,
-    ``nonbasis`` and with ``ranging`` the four range arrays.  A warm run need not terminate where
-    a cold solve of the perturbed problem would (the selection rule is no dual simplex): read
-    ``status``; SMX_PIVOT there means ``warm_pivots`` was reached."""
+    ``nonbasis`` and with ``ranging`` the four range arrays.
+
+    ``warm_rule`` is the selection rule of the WARM solve only (``"reference"`` or ``"dual"``; any
+    other value raises ValueError before the device is asked for); the base solve keeps the
+    reference rule, so ``base`` does not depend on it.  Under the default rule, which is no dual
+    simplex, a warm run need not terminate where a cold solve of the perturbed problem would.
+    Under ``"dual"`` (SMX_RULE_DUAL, include/smx.h) a scenario that moves constants only, after a
+    base run that ended at an optimum, starts dual feasible and terminates, up to degenerate
+    cycling; a scenario that also moves costs into a negative f-row entry takes the reference's
+    steps.  Either way read ``status``; SMX_PIVOT there means ``warm_pivots`` was reached."""
     _kernel_name(kernel)
+    wcode = _lib.rule_code(warm_rule)
     drhs = np.ascontiguousarray(drhs, dtype=np.float64)
     dcost = np.ascontiguousarray(dcost, dtype=np.float64)
     tabs, dims, (B, Rmax, ldb) = _launch_arrays(tabs, dims)
@@ -771,7 +807,8 @@ def solve_batch_scenarios_arrays(tabs: np.ndarray, dims: np.ndarray, drhs: np.nd
         # of no sets still names a legal group)
         return d_ts, d_ds, d_fs, (d_basis, d_nonbasis, max(c, 1))
 
-    return _warm_chain(L, dev, tabs, dims, which, P, S, make, Rmax, which, Pw, ranging, False)
+    return _warm_chain(L, dev, tabs, dims, which, P, S, make, Rmax, which, Pw, ranging, False,
+                       wcode)
 
 
 def _perturbed(cons, func, drhs, dcost):
@@ -789,9 +826,9 @@ def _perturbed(cons, func, drhs, dcost):
     return cons, func
 
 
-def _fallback_warm(cons, func, sets, max_pivots, warm_pivots, successor):
+def _fallback_warm(cons, func, sets, max_pivots, warm_pivots, successor, warm_rule="reference"):
     """One problem and its sets through ``SimplexMethod``; ``successor(sm, set)`` is the warm
-    object of a set (``what_if`` / ``add_constraints``)."""
+    object of a set (``what_if`` / ``add_constraints``), solved under ``warm_rule``."""
     try:
         sm = SimplexMethod(cons, func)
         sm.solve(record_history=False, max_pivots=max_pivots)
@@ -799,7 +836,7 @@ def _fallback_warm(cons, func, sets, max_pivots, warm_pivots, successor):
         out = []
         for entry in sets:
             warm = successor(sm, entry)
-            warm.solve(record_history=False, max_pivots=warm_pivots)
+            warm.solve(record_history=False, max_pivots=warm_pivots, rule=warm_rule)
             out.append(Scenario(warm.solution(), warm.status, True))
         return base, out
     except IndexError as exc:        # where the reference itself raises (simplex.py:49, 95, 159)
@@ -827,7 +864,8 @@ def _cold_tail(results, cold_problem, max_pivots, device, kernel):
 
 
 def solve_batch_scenarios(problems, scenarios, max_pivots: int = 256, warm_pivots=None,
-                          cold_fallback: bool = True, device=None, kernel: str = "auto"):
+                          cold_fallback: bool = True, device=None, kernel: str = "auto",
+                          warm_rule: str = "reference"):
     """Solve every ``(constraints, function)`` and its what-if scenarios; ``scenarios[k]`` is a
     list of ``(drhs, dcost)`` for problem k (``drhs`` [n] added to the constraints' constants,
     ``dcost`` [m] to ``function``; either may be ``None``).  Returns per problem ``(Solution,
@@ -838,12 +876,15 @@ def solve_batch_scenarios(problems, scenarios, max_pivots: int = 256, warm_pivot
     counts are padded with all-zero scenarios and dropped again
     (``solve_batch_scenarios_arrays``).  Problems routed ``"single"`` go through
     ``SimplexMethod.what_if``.  A warm run is capped at ``warm_pivots`` (default ``max_pivots``)
-    and need not terminate; with ``cold_fallback`` every scenario whose warm run did not end at
-    ``"optimum"`` is solved cold from the perturbed original through ``solve_batch_solutions``
-    with the full ``max_pivots`` and marked ``warm=False``."""
+    and under the default rule need not terminate; with ``cold_fallback`` every scenario whose
+    warm run did not end at ``"optimum"`` is solved cold from the perturbed original through
+    ``solve_batch_solutions`` with the full ``max_pivots`` and marked ``warm=False``.
+    ``warm_rule`` (``"reference"`` / ``"dual"``, as in ``solve_batch_scenarios_arrays``) is the rule
+    of the warm solves only -- the base solves and the cold re-solves keep the reference rule."""
     problems = list(problems)
     scenarios = [list(s) for s in scenarios]
     _kernel_name(kernel)                                     # refused before the scenarios are
+    _lib.rule_code(warm_rule)
     if len(scenarios) != len(problems):
         raise ValueError("scenarios must hold one list of scenarios per problem")
     P = int(max_pivots)
@@ -851,7 +892,8 @@ def solve_batch_scenarios(problems, scenarios, max_pivots: int = 256, warm_pivot
     results = [None] * len(problems)
 
     def single(k, c, f):
-        results[k] = _fallback_warm(c, f, scenarios[k], P, Pw, lambda sm, sc: sm.what_if(*sc))
+        results[k] = _fallback_warm(c, f, scenarios[k], P, Pw, lambda sm, sc: sm.what_if(*sc),
+                                    warm_rule)
 
     def launch(which, idx, tabs, dims):
         _, Rmax, ldb = tabs.shape
@@ -865,7 +907,8 @@ def solve_batch_scenarios(problems, scenarios, max_pivots: int = 256, warm_pivot
                     drhs[q, s, :n] = np.asarray(dr, dtype=np.float64).reshape(n)
                 if dc is not None:
                     dcost[q, s, :m] = np.asarray(dc, dtype=np.float64).reshape(m)
-        out = solve_batch_scenarios_arrays(tabs, dims, drhs, dcost, P, Pw, device, kernel=which)
+        out = solve_batch_scenarios_arrays(tabs, dims, drhs, dcost, P, Pw, device, kernel=which,
+                                           warm_rule=warm_rule)
         for q, k in enumerate(idx):
             results[k] = _warm_answers(out, q, int(dims[q, 0]), int(dims[q, 1]),
                                        [0] * len(scenarios[k]), Pw)
@@ -895,7 +938,7 @@ def warm_kernel(base: str, Rmax_out: int, ldb: int) -> str:
 def solve_batch_cuts_arrays(tabs: np.ndarray, dims: np.ndarray, cuts: np.ndarray,
                             ncuts: np.ndarray, max_pivots: int = 256, warm_pivots=None,
                             device=None, kernel: str = "auto", ranging: bool = False,
-                            log: bool = False) -> dict:
+                            log: bool = False, warm_rule: str = "reference") -> dict:
     """Array-level solve with new constraints: every LP of ``tabs`` / ``dims`` (as in
     ``solve_batch_arrays``) and S cut sets of each.  ``cuts``: float64 [B][S][K][ldb], row
     ``cuts[k, s, c]`` is a constraint of problem k in the format of its own rows (entry m_k the
@@ -917,10 +960,17 @@ def solve_batch_cuts_arrays(tabs: np.ndarray, dims: np.ndarray, cuts: np.ndarray
     [warm_pivots][2], B * S * warm_pivots * 8 bytes to copy back), ``x`` [ldb - 1], ``duals``
     [Rmax + K - 1] (the new constraints' included, at n_k..n_k + ncuts - 1), ``objective``,
     ``basis`` [Rmax + K - 1], ``nonbasis`` [ldb - 1] and with ``ranging`` the four range arrays.
-    A new constraint's label code is m_k + n_k + c.  A warm run need not terminate where a cold
-    solve of the enlarged problem would (the selection rule is no dual simplex): read ``status``;
+    A new constraint's label code is m_k + n_k + c.
+
+    ``warm_rule`` is the selection rule of the WARM solve only (``"reference"`` or ``"dual"``; any
+    other value raises ValueError before the device is asked for); ``base`` does not depend on it.
+    Under the default rule, which is no dual simplex, a warm run need not terminate where a cold
+    solve of the enlarged problem would.  An extended table keeps its base run's f-row, so after a
+    base run that ended at an optimum it is dual feasible and under ``"dual"`` (SMX_RULE_DUAL,
+    include/smx.h) the warm run terminates, up to degenerate cycling.  Either way read ``status``;
     SMX_PIVOT there means ``warm_pivots`` was reached."""
     _kernel_name(kernel)
+    wcode = _lib.rule_code(warm_rule)
     cuts = np.ascontiguousarray(cuts, dtype=np.float64)
     ncuts = np.ascontiguousarray(ncuts, dtype=np.int32)
     tabs, dims, (B, Rmax, ldb) = _launch_arrays(tabs, dims)
@@ -963,7 +1013,8 @@ def solve_batch_cuts_arrays(tabs: np.ndarray, dims: np.ndarray, cuts: np.ndarray
         return (d_tc, d_dc, d_func.repeat_interleave(c, dim=0),
                 (d_bc, d_nonbasis.repeat_interleave(c, dim=0), 1))
 
-    return _warm_chain(L, dev, tabs, dims, which, P, S, make, Rout, warm, Pw, ranging, log)
+    return _warm_chain(L, dev, tabs, dims, which, P, S, make, Rout, warm, Pw, ranging, log,
+                       wcode)
 
 
 def _enlarged(cons, func, rows):
@@ -972,7 +1023,8 @@ def _enlarged(cons, func, rows):
 
 
 def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
-                     cold_fallback: bool = True, device=None, kernel: str = "auto"):
+                     cold_fallback: bool = True, device=None, kernel: str = "auto",
+                     warm_rule: str = "reference"):
     """Solve every ``(constraints, function)`` and, for each of its cut sets, the problem with
     that set's constraints added; ``cuts[k]`` is a list of cut sets of problem k, each a list of
     rows in the constraints' own format ([m coefficients, constant]; an empty set adds nothing).
@@ -984,13 +1036,16 @@ def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
     and sizes are padded with empty sets and dropped again (``solve_batch_cuts_arrays``).
     Problems routed ``"single"``, and those of a launch whose enlarged tables leave every batch
     kernel's envelope, go through ``SimplexMethod.add_constraints``.  A warm run is capped at
-    ``warm_pivots`` (default ``max_pivots``) and need not terminate; with ``cold_fallback``
-    every set whose warm run did not end at ``"optimum"`` is solved cold from the enlarged
-    original through ``solve_batch_solutions`` with the full ``max_pivots`` and marked
-    ``warm=False``."""
+    ``warm_pivots`` (default ``max_pivots``) and under the default rule need not terminate; with
+    ``cold_fallback`` every set whose warm run did not end at ``"optimum"`` is solved cold from
+    the enlarged original through ``solve_batch_solutions`` with the full ``max_pivots`` and
+    marked ``warm=False``.  ``warm_rule`` (``"reference"`` / ``"dual"``, as in
+    ``solve_batch_cuts_arrays``) is the rule of the warm solves only -- the base solves and the
+    cold re-solves keep the reference rule."""
     problems = list(problems)
     cuts = [[[list(r) for r in rows] for rows in sets] for sets in cuts]
     _kernel_name(kernel)                                     # refused before the cuts are
+    _lib.rule_code(warm_rule)
     if len(cuts) != len(problems):
         raise ValueError("cuts must hold one list of cut sets per problem")
     for (c, _), sets in zip(problems, cuts):
@@ -1001,7 +1056,8 @@ def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
     results = [None] * len(problems)
 
     def single(k, c, f):
-        results[k] = _fallback_warm(c, f, cuts[k], P, Pw, SimplexMethod.add_constraints)
+        results[k] = _fallback_warm(c, f, cuts[k], P, Pw, SimplexMethod.add_constraints,
+                                    warm_rule)
 
     def launch(which, idx, tabs, dims):
         _, Rmax, ldb = tabs.shape
@@ -1021,7 +1077,8 @@ def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
                 nc[q, s] = len(rows)
                 if rows:
                     g[q, s, :len(rows), :m + 1] = np.asarray(rows, dtype=np.float64)
-        out = solve_batch_cuts_arrays(tabs, dims, g, nc, P, Pw, device, kernel=which)
+        out = solve_batch_cuts_arrays(tabs, dims, g, nc, P, Pw, device, kernel=which,
+                                      warm_rule=warm_rule)
         for q, k in enumerate(idx):
             results[k] = _warm_answers(out, q, int(dims[q, 0]), int(dims[q, 1]),
                                        [len(rows) for rows in cuts[k]], Pw)

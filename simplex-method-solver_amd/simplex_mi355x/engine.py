@@ -533,8 +533,11 @@ class SimplexMethod:
         16384 x 16384 tableau this is correct, not fast.  The result lives on the same backend:
         its ``row`` / ``column`` carry the labels, its ``function`` is the scenario's cost vector,
         its pivot log starts empty, and ``solve()``, ``solution()`` and ``ranging()`` carry on
-        from there.  Such a warm run need not terminate (the selection rule is no dual simplex):
-        cap it with ``max_pivots`` and read ``status``."""
+        from there.  Under the default rule, which is no dual simplex, such a warm run need not
+        terminate.  After a solve that ended at ``"optimum"`` and with ``dcost`` unchanged the
+        table is dual feasible, and ``solve(rule="dual")`` terminates from it, up to degenerate
+        cycling (include/smx.h, SMX_RULE_DUAL).  Either way cap the run with ``max_pivots`` and
+        read ``status``."""
         n, m = self.n, self.m
         basis, nonbasis = self._label_codes()
         dr = np.zeros(n, dtype=np.float64)
@@ -567,9 +570,11 @@ class SimplexMethod:
         ``smx_host_cuts`` (include/smx.h) -- on every backend, so this is correct everywhere and
         fast nowhere special.  The result lives on the same backend: ``column`` is extended by
         'y{n+1}'.., ``row`` and ``function`` are unchanged, its pivot log starts empty, and
-        ``solve()``, ``solution()`` and ``ranging()`` carry on from there.  Such a warm run need
-        not terminate (the selection rule is no dual simplex): cap it with ``max_pivots`` and
-        read ``status``."""
+        ``solve()``, ``solution()`` and ``ranging()`` carry on from there.  Under the default
+        rule, which is no dual simplex, such a warm run need not terminate.  After a solve that
+        ended at ``"optimum"`` the extended table is dual feasible, and ``solve(rule="dual")``
+        terminates from it, up to degenerate cycling (include/smx.h, SMX_RULE_DUAL).  Either way
+        cap the run with ``max_pivots`` and read ``status``."""
         n, m = self.n, self.m
         rows = [list(r) for r in rows]
         if any(len(r) != m + 1 for r in rows):
@@ -591,10 +596,26 @@ class SimplexMethod:
                                1 + max(n + K, m))
 
     # ---------------------------------------------------------------- the hot path -------
-    def pick_element(self) -> (bool, int, int, float):
+    def _rule_twin(self):
+        """A host tableau holding the current table: where a backend's own selection takes no
+        rule (device, sharded), the host twins of include/smx.h decide and pivot on it and the
+        result is uploaded again -- correct, not fast, as ``what_if`` is."""
+        from .host import HostTableau
+        return HostTableau(self._dense_table(), self.n, self.m, self.flen)
+
+    def pick_element(self, rule="reference") -> (bool, int, int, float):
         """simplex.py:70-141: selection kernels on the device, outcome mapped to the
-        reference's return tuple / ValueError."""
-        status, r, c, e = self._dev.pick()
+        reference's return tuple / ValueError.  ``rule="dual"`` decides by SMX_RULE_DUAL
+        (include/smx.h): natively on the host backend, on a host copy of the table elsewhere."""
+        code = _lib.rule_code(rule)
+        self._twin = None
+        if code == _lib.RULE_REFERENCE:
+            status, r, c, e = self._dev.pick()
+        elif self.backend == "host":
+            status, r, c, e = self._dev.pick(code)
+        else:
+            self._twin = self._rule_twin()
+            status, r, c, e = self._twin.pick(code)
         if status == _lib.PIVOT:
             if self._pristine:
                 e = self._initial[r][c]
@@ -616,27 +637,36 @@ class SimplexMethod:
             # the reference's step 2 / step 4 index the f-row out of range (simplex.py:159-175)
             raise IndexError("list index out of range")
         first_int = self._pristine and self._int0 is not None
-        self._dev.apply_selected()
-        if first_int:
-            self._int_first_fix(r, c)
+        twin = getattr(self, "_twin", None)
+        if twin is not None:       # the pick came from the host twin: pivot there, then upload
+            twin.apply_selected()
+            if first_int:
+                self._int_first_fix(r, c, twin)
+            self._dev.upload(twin.download())
+            self._twin = None
+        else:
+            self._dev.apply_selected()
+            if first_int:
+                self._int_first_fix(r, c)
         self._pristine = False
         self.pivot_log.append((r, c))
 
-    def _int_first_fix(self, r, c):
-        """The first pivot of a table with int entries just ran (r, c): give its zero results
-        the signs the reference's int arithmetic gives them (smx_int_first_fix)."""
+    def _int_first_fix(self, r, c, dev=None):
+        """The first pivot of a table with int entries just ran (r, c) on ``dev`` (default: this
+        object's tableau): give its zero results the signs the reference's int arithmetic gives
+        them (smx_int_first_fix)."""
         mask = None if self._int0 is True else self._int0
-        self._dev.int_first_fix(mask, r, c)
+        (self._dev if dev is None else dev).int_first_fix(mask, r, c)
         self._int_hist = (mask, r, c)
         self._int0 = None
 
-    def _int_first_after_run(self, before, done):
+    def _int_first_after_run(self, before, done, dev=None):
         """After a chained run that began at the caller's table: the int fix of its first pivot
         (the chained loops run that pivot alone while one is pending).  True when applied."""
         if self._int0 is None or before != 0 or done < 1 or not self._pristine:
             return False
-        r, c = (int(x) for x in self._dev.read_log(0, 1)[0])
-        self._int_first_fix(r, c)
+        r, c = (int(x) for x in (self._dev if dev is None else dev).read_log(0, 1)[0])
+        self._int_first_fix(r, c, dev)
         return True
 
     def recalculate_matrix(self):
@@ -661,15 +691,19 @@ class SimplexMethod:
 
     LAZY_ELEMENTS = 1 << 20   # above this many tableau entries get_solution snapshots lazily
 
-    def get_solution(self, max_pivots=None, detect_cycles=False, lazy=None, chunk=256):
+    def get_solution(self, max_pivots=None, detect_cycles=False, lazy=None, chunk=256,
+                     rule="reference"):
         """simplex.py:179-199.  Opt-in additions (defaults = the reference's behaviour):
         ``max_pivots`` bounds the loop (the list ends, ``status == 'cap'``); ``detect_cycles``
         ends it when the basis repeats (``status == 'cycle'``, ``self.cycle``).  ``lazy``
         (default: automatic above ``LAZY_ELEMENTS`` entries) runs the chained device loop and
-        returns ``LazyInfo`` snapshots whose tables are materialised on access."""
+        returns ``LazyInfo`` snapshots whose tables are materialised on access.  ``rule``
+        selects the selection rule of every step (``pick_element``); ``"dual"`` runs step by step."""
+        code = _lib.rule_code(rule)
         if lazy is None:
             lazy = (self.n + 1) * (self.m + 1) > self.LAZY_ELEMENTS
         lazy = lazy and self.backend != "host"   # device checkpoints + replay need a device
+        lazy = lazy and code == _lib.RULE_REFERENCE
         if lazy and self.flen in (self.m, self.m + 1) and self.flen >= 2:
             return self._get_solution_lazy(max_pivots, detect_cycles, chunk)
         # every snapshot is a fresh acyclic list of lists: pause the cyclic collector so its
@@ -677,18 +711,18 @@ class SimplexMethod:
         gc_was_on = gc.isenabled()
         gc.disable()
         try:
-            return self._get_solution_eager(max_pivots, detect_cycles)
+            return self._get_solution_eager(max_pivots, detect_cycles, rule)
         finally:
             if gc_was_on:
                 gc.enable()
 
-    def _get_solution_eager(self, max_pivots, detect_cycles):
+    def _get_solution_eager(self, max_pivots, detect_cycles, rule="reference"):
         result = []
         result.append(self._snapshot(0, 0, 0))
         done = 0
         while True:
             try:
-                is_successful, i, j, e = self.pick_element()
+                is_successful, i, j, e = self.pick_element(rule)
             except ValueError as exc:
                 result.append(Error(str(exc)))
                 self.status = "error"
@@ -771,24 +805,40 @@ class SimplexMethod:
         return result
 
     # ---------------------------------------------------------------- additions ----------
-    def step(self):
-        """One pick + pivot; returns pick_element's tuple (raises like it)."""
-        res = self.pick_element()
+    def step(self, rule="reference"):
+        """One pick + pivot under ``rule``; returns pick_element's tuple (raises like it)."""
+        res = self.pick_element(rule)
         if res[0]:
             self._apply(res[1], res[2])
         return res
 
     def solve(self, record_history=True, max_pivots=None, chunk=256, graph=True,
-              detect_cycles=False):
+              detect_cycles=False, rule="reference"):
         """``get_solution`` (record_history=True) or the chained fast path: pivots run on the
         device in chunks of ``chunk`` with no host synchronisation inside a chunk; returns
         ``[Info(initial, i/j of the first pivot), Info(final)]`` plus a trailing ``Error``.
-        ``detect_cycles`` stops at the end of the chunk in which the basis first repeats."""
+        ``detect_cycles`` stops at the end of the chunk in which the basis first repeats.
+
+        ``rule``: ``"reference"`` (the default: the reference's pick_element) or ``"dual"``
+        (SMX_RULE_DUAL of include/smx.h: from a table with negative constants and no negative
+        f-row entry, as ``what_if(drhs)`` and ``add_constraints`` leave after an optimum, every
+        step is a dual-simplex step and the run terminates, up to degenerate cycling; anywhere
+        else a step is the reference's).  On the host backend the chain is the library's host
+        twin with the same chunk protocol (a pristine int table still runs its first pivot
+        alone).  On the device and sharded backends ``"dual"`` is correct, not fast, as
+        ``what_if`` and ``add_constraints`` are: the table comes down, the host twin runs the
+        chain and the result is uploaded again.  ``pivots``, ``pivot_log``, ``row`` / ``column``,
+        ``status``, ``solution()`` and ``ranging()`` are right afterwards on every backend.  An
+        unknown rule raises ValueError."""
+        code = _lib.rule_code(rule)
         if record_history:
-            return self.get_solution(max_pivots=max_pivots, detect_cycles=detect_cycles)
+            return self.get_solution(max_pivots=max_pivots, detect_cycles=detect_cycles,
+                                     rule=rule)
         if self.flen not in (self.m, self.m + 1) or self.flen < 2:
-            return self._solve_stepwise(max_pivots, detect_cycles)
-        big = (self.n + 1) * (self.m + 1) > self.LAZY_ELEMENTS and self.backend != "host"
+            return self._solve_stepwise(max_pivots, detect_cycles, rule)
+        twin = code != _lib.RULE_REFERENCE and self.backend != "host"
+        big = ((self.n + 1) * (self.m + 1) > self.LAZY_ELEMENTS and self.backend != "host"
+               and not twin)
         hist = History(self, every=1 << 62) if big else None    # one checkpoint: the start
         if big:
             first = LazyInfo(self.row, self.column, hist, self.pivots, None, None, 0, 0, 0)
@@ -796,17 +846,20 @@ class SimplexMethod:
             first = self._snapshot(0, 0, 0)
         start = self.pivots
         budget = float("inf") if max_pivots is None else int(max_pivots)
-        dev = self._dev
+        dev = self._rule_twin() if twin else self._dev
         status = None
         while self.pivots - start < budget:
             k = int(min(chunk, budget - (self.pivots - start), dev.log_cap))
             if self._int0 is not None and self._pristine:
                 k = 1                      # the first pivot of an int table runs alone
             before = dev.step
-            dev.run(k, graph=graph and k == chunk)
+            if code == _lib.RULE_REFERENCE:
+                dev.run(k, graph=graph and k == chunk)
+            else:
+                dev.run(k, rule=code)
             ctl = dev.sync_state()
             done = int(ctl["npivots"])
-            self._int_first_after_run(before, done)
+            self._int_first_after_run(before, done, dev)
             cycled = False
             for r, c in dev.read_log(before, done):
                 r, c = int(r), int(c)
@@ -821,6 +874,8 @@ class SimplexMethod:
             if cycled:
                 status = "cycle"
                 break
+        if twin and self.pivots > start:     # the twin's final table goes back to the backend
+            self._dev.upload(dev.download())
         out = [first]
         if self.pivots > start:
             first.i, first.j = self.pivot_log[start]
@@ -844,13 +899,13 @@ class SimplexMethod:
             raise RuntimeError(f"unexpected terminal status {status}")
         return out
 
-    def _solve_stepwise(self, max_pivots, detect_cycles=False):
+    def _solve_stepwise(self, max_pivots, detect_cycles=False, rule="reference"):
         first = self._snapshot(0, 0, 0)
         out = [first]
         done = 0
         while max_pivots is None or done < max_pivots:
             try:
-                ok, i, j, _ = self.pick_element()
+                ok, i, j, _ = self.pick_element(rule)
             except ValueError as exc:
                 x1, x2 = self.find_optimum()
                 out.append(self._snapshot(x1, x2, self.f(x1, x2)))

@@ -81,12 +81,12 @@ class HostTableau:
     def _ptr(self, a: np.ndarray):
         return a.ctypes.data_as(ctypes.c_void_p)
 
-    def pick(self):
-        """pick_element: (status, r, c, e)."""
+    def pick(self, rule: int = _lib.RULE_REFERENCE):
+        """pick_element under the selection rule ``rule`` (SMX_RULE_*): (status, r, c, e)."""
         self._term = False
         rc = np.zeros(2, dtype=np.int32)
-        st = int(self._L.smx_host_select(self._ptr(self.cur()), ctypes.byref(self._shape),
-                                         self._ptr(rc)))
+        st = int(self._L.smx_host_select_rule(self._ptr(self.cur()), ctypes.byref(self._shape),
+                                              int(rule), self._ptr(rc)))
         r, c = int(rc[0]), int(rc[1])
         self._sel = (r, c) if st == _lib.PIVOT else None
         self._status = st
@@ -109,15 +109,16 @@ class HostTableau:
         self._sel = (r, c)
         self.apply_selected()
 
-    def run(self, k: int, graph: bool = True) -> None:
-        """k chained pivots (get_solution's loop, simplex.py:184-198) in one native call."""
+    def run(self, k: int, graph: bool = True, rule: int = _lib.RULE_REFERENCE) -> None:
+        """k chained pivots (get_solution's loop, simplex.py:184-198) in one native call, under
+        the selection rule ``rule`` (SMX_RULE_*)."""
         if k <= 0:
             return
         log = np.zeros((k, 2), dtype=np.int32)
         st = ctypes.c_int32()
-        done = int(self._L.smx_host_run(self._ptr(self.buf[0]), self._ptr(self.buf[1]),
-                                        ctypes.byref(self._shape), self.step & 1, int(k),
-                                        self._ptr(log), ctypes.byref(st)))
+        done = int(self._L.smx_host_run_rule(self._ptr(self.buf[0]), self._ptr(self.buf[1]),
+                                             ctypes.byref(self._shape), self.step & 1, int(k),
+                                             int(rule), self._ptr(log), ctypes.byref(st)))
         self._log = np.concatenate([self._log, log[:done]])
         self.step += done
         self._status = int(st.value)
