@@ -6,6 +6,10 @@ with the signs of zeros, 120 of them differing from an all-float run.  Checked b
 signed zeros included, through the oracle restatement, the host engine (CPU suite) and every
 device path (``-m gpu``: eager and lazy get_solution, chained solve with the launch chain, the
 LDS-resident loop and block pivots, row-sharded devices).
+
+The fixture ends at 65 x 65, inside one pass of the fix kernel's geometry; for tables past 256
+columns and 4096 rows, padded pitches and the rank without the pivot row see test_intfirst.py and
+test_gpu_intfirst.py (inputs and census: intfirst_util.py).
 """
 from __future__ import annotations
 
