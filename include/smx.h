@@ -463,6 +463,69 @@ int smx_host_cuts(const double* T, int64_t ld, int32_t n, int32_t m, const int32
                   const int32_t* nonbasis, const double* G, int32_t K, double* E_out,
                   int64_t ld_out, int32_t* basis_out);
 
+/* ---- new variables: warm re-solves after columns are added (smx_cols.hpp) ---------------------
+ * "I have a new variable; what is the optimum now?" (column generation).  T is a final table
+ * ([n+1][m+1], f-row = row n, "-b" = column m) under the labels basis[p] / nonbasis[j] as
+ * smx_batch_solution writes them.  A new variable is a vector a[0..n]: a[i], i < n, is its
+ * coefficient in constraint i of the ORIGINAL problem (y_i = sum_k A[i][k] * x_k + a[i] * x_new +
+ * t_i) and a[n] its entry in `function`.  A set holds K' columns; its widened table W has
+ * m' = m + K' variables.  For every row p of the block:
+ *   columns 0..m-1 are T's bits; column m + K' is T's column m (the "-b" column moves, bit for
+ *   bit); columns past m + K' hold +0.0 (T's padding columns are not carried over); the new
+ *   columns m + kappa hold +0.0 in rows past n;
+ *   entry W[p][m+kappa], for p = 0..n:
+ *        v = a[basis[p] - m]  if p < n and m <= basis[p] < m + n (the column's own bits, a -0.0 kept)
+ *        v = a[n]             if p == n
+ *        v = +0.0             otherwise
+ *        for j = 0..m-1 ascending: if nonbasis[j] = m + i, 0 <= i < n, and a[i] != 0:
+ *                                                                  v = v - T[p][j] * a[i]
+ *        W[p][m+kappa] = v
+ * Every product is rounded on its own, the sum runs strictly in that order, there is no FMA.  An
+ * a[i] that compares equal to zero is skipped, so it cannot turn an inf of T into NaN; a NaN a[i]
+ * is applied.  A label code outside 0..n+m-1 names nothing and is skipped.  This is step 2 of a
+ * scenario (above) with drhs = a, applied to a column that starts from the variable's own entries.
+ * The labels are the codes the LP would have had with the variables appended to the original: an
+ * old code c < m stays, an old code m + i becomes m + K' + i, new column kappa gets m + kappa
+ * ('x{m+kappa+1}'), any other input code becomes -1.  dims becomes (n, m + K', flen + K'); func_v
+ * holds func[0..m-1], then a[n] of each column, then +0.0.  smx_batch_solution_from(group = 1)
+ * serves the warm runs unchanged.  Values are formed whatever the base run's status.  Columns are
+ * independent of each other.  Under identity labels W is the widened original problem bit for
+ * bit, and W is one bit pattern in any implementation.  W is an equivalent form of the widened LP
+ * under T's labels.  A new variable leaves every "-b" entry as it was, so after a base run that
+ * ended at SMX_OPTIMUM W is primal feasible, only the new columns' f-row entries can be negative,
+ * and the default rule carries on from W as an ordinary primal simplex.  A caller
+ * still caps the run and reads its status.
+ *
+ * smx_batch_cols (device pointers, after smx_batch_solution): final fp64 [B][Rmax][ldb], dims
+ * int32 [B][3], basis int32 [B][Rmax], nonbasis int32 [B][ldb], func fp64 [B][ldb] (the original
+ * objective rows), cols fp64 [B][S][K][Rmax] (entry n_b of a column is its cost; entries past n_b
+ * are not read), ncols int32 [B][S]; outputs tabs_v fp64 [B*S][Rmax][ldb_out], func_v fp64
+ * [B*S][ldb_out], dims_v int32 [B*S][3], basis_v int32 [B*S][Rmax] and nonbasis_v int32
+ * [B*S][ldb_out] (the recoded labels, -1 as padding); column set q = b * S + s belongs to LP b.
+ * The whole output block is written exactly once.  A set with ncols outside 0..K, with
+ * m_b + ncols >= ldb_out or of an LP with flen_b < m_b (a short f-row, whose padding entries
+ * would become live) counts as a set of 0 columns (a relayout of T); an LP without 1 <= n_b < Rmax
+ * and 1 <= m_b < ldb is handled as m_b = ldb - 1 with 0 columns, keeps its dims and gets labels -1
+ * and func_v +0.0.  Returns hipErrorInvalidValue (1) before any HIP call for B < 0, S < 0, K < 0,
+ * ldb_out < ldb, B * S past 2^31 - 1, (Rmax, ldb) or (Rmax, ldb_out) outside smx_batch_cols_fits
+ * or, with B * S > 0, a null pointer (cols may be null when K == 0); B == 0 or S == 0 returns 0
+ * without a launch. */
+int smx_batch_cols(const double* final, const int32_t* dims, int32_t B, int32_t S, int32_t Rmax,
+                   int32_t ldb, const int32_t* basis, const int32_t* nonbasis, const double* func,
+                   const double* cols, const int32_t* ncols, int32_t K, int32_t ldb_out,
+                   double* tabs_v, double* func_v, int32_t* dims_v, int32_t* basis_v,
+                   int32_t* nonbasis_v, void* stream);
+/* Host only: 1 inside the envelope (that of smx_batch_scenario_fits, applied to the output
+ * block), else 0. */
+int smx_batch_cols_fits(int32_t Rmax, int32_t ldb_out);
+/* The same rule on one HOST table with leading dimension ld >= m + 1 (synchronous): A [K][n+1];
+ * W_out [n+1][ld_out] (ld_out >= m + K + 1; columns 0..m+K of every row are written; it must not
+ * overlap T), basis_out [n] and nonbasis_out [m+K].  -1 for a null pointer (A may be null when
+ * K == 0), n < 1, m < 1, K < 0, ld < m + 1 or ld_out < m + K + 1. */
+int smx_host_cols(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                  const int32_t* nonbasis, const double* A, int32_t K, double* W_out,
+                  int64_t ld_out, int32_t* basis_out, int32_t* nonbasis_out);
+
 /* ---- row-sharded engine (one process per GPU; exchange = caller's all-gather) ----------
  * Local tableau: shape->rows constraint rows (global rows row0 .. row0+rows-1) + a replica
  * of the f-row as local row `rows`.  Per pivot:

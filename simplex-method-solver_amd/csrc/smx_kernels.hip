@@ -20,6 +20,9 @@
 //   smx_cuts.hpp      k_batch_cuts (a batch's final tables, labels and new constraint rows -> the
 //                     extended tables warm re-solves start from, one workgroup per cut set) and
 //                     host_cuts
+//   smx_cols.hpp      k_batch_cols (a batch's final tables, labels and new variables' columns ->
+//                     the widened tables warm re-solves start from, one workgroup per column set)
+//                     and host_cols
 //   smx_resident.hpp  k_resident: the whole pivot loop in one persistent launch, tableau in LDS
 //   smx_block.hpp     k_blk_*: P pivots per HBM sweep, decisions planned from the sweep's input
 //   smx_sweep.hpp     k_blk_sweep, k_blk_sweep_rest: the sweep itself
@@ -70,6 +73,7 @@ static_assert(sizeof(smx_part) == 32, "smx_part layout");
 #include "smx_ranging.hpp"
 #include "smx_scenario.hpp"
 #include "smx_cuts.hpp"
+#include "smx_cols.hpp"
 #include "smx_resident.hpp"
 #include "smx_block.hpp"
 #include "smx_sweep.hpp"
@@ -1475,6 +1479,41 @@ int smx_host_cuts(const double* T, int64_t ld, int32_t n, int32_t m, const int32
         (int64_t)n + m + K > INT32_MAX)
         return -1;
     host_cuts(T, ld, n, m, basis, nonbasis, G, K, E_out, ld_out, basis_out);
+    return 0;
+}
+
+// ---- new variables: the widened tables warm re-solves start from (smx_cols.hpp) ---------------
+// The envelope is smx_batch_scenario_fits applied to the output block; the kernel holds no LDS.
+int smx_batch_cols_fits(int32_t Rmax, int32_t ldb_out) {
+    return sol_lds_bytes(Rmax, ldb_out) >= 0;
+}
+
+int smx_batch_cols(const double* final, const int32_t* dims, int32_t B, int32_t S_, int32_t Rmax,
+                   int32_t ldb, const int32_t* basis, const int32_t* nonbasis, const double* func,
+                   const double* cols, const int32_t* ncols, int32_t K, int32_t ldb_out,
+                   double* tabs_v, double* func_v, int32_t* dims_v, int32_t* basis_v,
+                   int32_t* nonbasis_v, void* stream) {
+    if (B < 0 || S_ < 0 || K < 0 || ldb_out < ldb || sol_lds_bytes(Rmax, ldb) < 0 ||
+        sol_lds_bytes(Rmax, ldb_out) < 0 || (int64_t)B * S_ > INT32_MAX)
+        return (int)hipErrorInvalidValue;
+    if (B == 0 || S_ == 0) return 0;
+    if (!final || !dims || !basis || !nonbasis || !func || (!cols && K > 0) || !ncols ||
+        !tabs_v || !func_v || !dims_v || !basis_v || !nonbasis_v)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_batch_cols, dim3((unsigned)(B * S_)), dim3(kColBlock), 0, S(stream),
+                       final, dims, B, S_, Rmax, ldb, basis, nonbasis, func, cols, ncols, K,
+                       ldb_out, tabs_v, func_v, dims_v, basis_v, nonbasis_v);
+    return (int)hipGetLastError();
+}
+
+int smx_host_cols(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                  const int32_t* nonbasis, const double* A, int32_t K, double* W_out,
+                  int64_t ld_out, int32_t* basis_out, int32_t* nonbasis_out) {
+    if (!T || !basis || !nonbasis || (!A && K > 0) || !W_out || !basis_out || !nonbasis_out ||
+        n < 1 || m < 1 || K < 0 || ld < (int64_t)m + 1 || ld_out < (int64_t)m + K + 1 ||
+        (int64_t)n + m + K > INT32_MAX)
+        return -1;
+    host_cols(T, ld, n, m, basis, nonbasis, A, K, W_out, ld_out, basis_out, nonbasis_out);
     return 0;
 }
 

@@ -123,6 +123,7 @@ EXPORTS = (
     "smx_batch_ranging", "smx_batch_ranging_fits", "smx_host_ranging",
     "smx_batch_scenario", "smx_batch_scenario_fits", "smx_host_scenario", "smx_batch_solution_from",
     "smx_batch_cuts", "smx_batch_cuts_fits", "smx_host_cuts",
+    "smx_batch_cols", "smx_batch_cols_fits", "smx_host_cols",
     "smx_comm_unique_id", "smx_comm_init", "smx_comm_destroy",
     "smx_shard_run", "smx_shard_run_timed", "smx_shard_pack", "smx_shard_merge", "smx_shard_update", "smx_shard_begin",
     "smx_shard_finish", "smx_shard_fused_prime", "smx_shard_fused_begin",
@@ -221,6 +222,10 @@ def load():
                            ctypes.c_int),
         "smx_batch_cuts_fits": ([i32, i32], ctypes.c_int),
         "smx_host_cuts": ([vp, i64, i32, i32, vp, vp, vp, i32, vp, i64, vp], ctypes.c_int),
+        "smx_batch_cols": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp,
+                            vp, vp, vp], ctypes.c_int),
+        "smx_batch_cols_fits": ([i32, i32], ctypes.c_int),
+        "smx_host_cols": ([vp, i64, i32, i32, vp, vp, vp, i32, vp, i64, vp, vp], ctypes.c_int),
         "smx_shard_begin": ([vp, sp, i32, vp, vp, vp, vp], ctypes.c_int),
         "smx_shard_finish": ([vp, vp, vp, i32, sp, i32, vp, vp, i64, vp, vp, vp], ctypes.c_int),
         "smx_shard_fused_prime": ([vp, sp, i32, vp, vp, vp], ctypes.c_int),

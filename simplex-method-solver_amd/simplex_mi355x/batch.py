@@ -41,14 +41,21 @@ the enlarged block carries on from there.  The same caveat holds un
 rule and the same cold fallback answers it; an extended table keeps its base run's f-row, so after
 an optimum ``warm_rule="dual"`` applies to every cut set.
 
+``solve_batch_columns`` (and ``solve_batch_columns_arrays``) answer "I have new variables: what is
+the optimum now?" -- column generation: ``k_batch_cols`` (csrc/smx_cols.hpp) writes every new
+variable, given by its coefficients in the original constraints and its cost, as one more column
+under its LP's final basis, and the solve kernel that takes the widened block carries on from
+there.  A new variable leaves the constants alone, so after an optimum the widened
+table is primal feasible and the default rule is an ordinary primal simplex from it.
+
 The host side of all this is stated once.  Array level: ``_launch_arrays`` and
 ``_launch_tier`` check a launch, ``_device_solve`` / ``_device_solution`` / ``_device_ranging``
 enqueue one kernel each on fresh outputs, ``_enqueue_base`` and ``_base_arrays`` are
 ``solve_batch_arrays`` (and so the ``base`` of the warm calls), and ``_warm_chain`` is everything
-the two warm calls share: a warm feature hands it the callable that enqueues its table-making
-kernel.  Object level: ``_drive`` routes, falls back and launches for all five ``solve_batch*``
+the warm calls share: a warm feature hands it the callable that enqueues its table-making
+kernel.  Object level: ``_drive`` routes, falls back and launches for all six ``solve_batch*``
 calls, ``_solution_at`` builds a ``Solution``, ``_status_name`` names a status, ``_warm_answers``
-and ``_cold_tail`` serve scenarios and cuts alike.
+and ``_cold_tail`` serve scenarios, cuts and columns alike.
 """
 from __future__ import annotations
 
@@ -120,6 +127,11 @@ def scenario_fits(Rmax: int, ldb: int) -> bool:
 def cuts_fits(Rmax_out: int, ldb: int) -> bool:
     """Whether output blocks of Rmax_out x ldb are inside k_batch_cuts's envelope."""
     return bool(_envelope("smx_batch_cuts_fits", Rmax_out, ldb, False))
+
+
+def cols_fits(Rmax: int, ldb_out: int) -> bool:
+    """Whether output blocks of Rmax x ldb_out are inside k_batch_cols's envelope."""
+    return bool(_envelope("smx_batch_cols_fits", Rmax, ldb_out, False))
 
 
 def _shape(cons, func):
@@ -683,13 +695,14 @@ def solve_batch_ranges(problems, max_pivots: int = 256, device=None, kernel: str
 
 
 def _warm_chain(L, dev, tabs, dims, tier, P, S, make, rows, warm_tier, Pw, ranging, log,
-                warm_rule=_lib.RULE_REFERENCE):
-    """The chain of both warm calls, on one stream and with no host round trip between the steps:
+                warm_rule=_lib.RULE_REFERENCE, cols=None):
+    """The chain of every warm call, on one stream and with no host round trip between the steps:
     the base launch of ``tabs`` / ``dims`` on ``tier`` (``_enqueue_base``), then for every slice of
     the S sets ``make(stream, s0, c, final, d_dims, func, basis, nonbasis)``, which enqueues the
-    kernel that writes the B * c warm tables of sets s0..s0 + c - 1 (``rows`` rows each) from the
-    base launch's device tensors and returns (tables, their dims, their function rows, the
-    ``start`` of ``_device_solution``); the warm solve on ``warm_tier`` capped at ``Pw`` under
+    kernel that writes the B * c warm tables of sets s0..s0 + c - 1 (``rows`` rows and ``cols``
+    columns each; ``cols`` None: as many columns as the base tables) from the base launch's
+    device tensors and returns (tables, their dims, their function rows, the ``start`` of
+    ``_device_solution``); the warm solve on ``warm_tier`` capped at ``Pw`` under
     the selection rule ``warm_rule`` (the base launch keeps the reference rule), its solution from
     ``start`` and, with ``ranging``, its ranges.  A slice holds as many sets as keep
     its tables under ``GM_TABLE_BUDGET``.  Only when everything is enqueued does anything come
@@ -698,7 +711,8 @@ def _warm_chain(L, dev, tabs, dims, tier, P, S, make, rows, warm_tier, Pw, rangi
     S == 0 runs one slice of no sets, on which every library call returns at once, so that its
     result has the shapes of any other."""
     B, _, ldb = tabs.shape
-    per = max(1, min(S, GM_TABLE_BUDGET // max(1, B * rows * ldb * 8)))
+    width = ldb if cols is None else cols
+    per = max(1, min(S, GM_TABLE_BUDGET // max(1, B * rows * width * 8)))
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
         d_tabs = torch.from_numpy(tabs).to(dev)
@@ -843,10 +857,11 @@ def _fallback_warm(cons, func, sets, max_pivots, warm_pivots, successor, warm_ru
         return exc, [Scenario(exc, "exception", True) for _ in sets]
 
 
-def _warm_answers(out, q, n, m, added, Pw):
-    """(Solution, [Scenario]) of member q of a warm launch; set s holds n + added[s] rows."""
+def _warm_answers(out, q, n, m, added, Pw, wide=False):
+    """(Solution, [Scenario]) of member q of a warm launch; set s holds n + added[s] rows
+    (``wide``: m + added[s] variables)."""
     return (_solution_at(out["base"], q, n, m),
-            [Scenario(_solution_at(out, (q, s), n + a, m),
+            [Scenario(_solution_at(out, (q, s), n if wide else n + a, m + a if wide else m),
                       _status_name(int(out["status"][q, s]), int(out["npivots"][q, s]), Pw), True)
              for s, a in enumerate(added)])
 
@@ -1087,6 +1102,168 @@ def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
     if cold_fallback:
         _cold_tail(results, lambda k, s: _enlarged(*problems[k], cuts[k][s]), max_pivots, device,
                    kernel)
+    return results
+
+
+def solve_batch_columns_arrays(tabs: np.ndarray, dims: np.ndarray, cols: np.ndarray,
+                               ncols: np.ndarray, max_pivots: int = 256, warm_pivots=None,
+                               device=None, kernel: str = "auto", ranging: bool = False,
+                               log: bool = False, warm_rule: str = "reference") -> dict:
+    """Array-level solve with new variables: every LP of ``tabs`` / ``dims`` (as in
+    ``solve_batch_arrays``) and S column sets of each.  ``cols``: float64 [B][S][K][Rmax], column
+    ``cols[k, s, c]`` holds the new variable's coefficient in every constraint of problem k
+    (entries 0..n_k - 1) and its entry in ``function`` (entry n_k; entries past it are not read);
+    ``ncols``: int32 [B][S], how many of the K columns set s of problem k holds (0..K, else
+    ValueError).  A problem whose ``function`` is shorter than m_k takes no columns (ValueError).
+
+    One stream, no host round trip between the steps: the base solve, ``smx_batch_solution``
+    (``ranging``: ``smx_batch_ranging``), then ``smx_batch_cols`` (the widened tables of ldb + K
+    columns under every LP's final labels, recoded; include/smx.h), the warm solve of all B * S
+    tables capped at ``warm_pivots`` (default: ``max_pivots``), ``smx_batch_solution_from`` (group
+    1: every table starts from its own recoded labels) and, with ``ranging``,
+    ``smx_batch_ranging`` on the warm runs' final tables.  The warm solve's kernel is chosen again
+    for (Rmax, ldb + K) (``warm_kernel``): a launch may leave the wavefront tier for the workgroup
+    tier or the LDS edge for the global-memory tier; a shape that leaves every tier raises
+    ValueError before anything is enqueued.  The widened tables are made in slices of S that keep
+    them under ``GM_TABLE_BUDGET``.
+
+    Returns ``base`` exactly as ``solve_batch_scenarios_arrays`` does; and per column set, shaped
+    [B][S]...: ``status``, ``npivots`` (the warm pivots only; with ``log`` also their log ``rc``
+    [warm_pivots][2]), ``x`` [ldb + K - 1] (the new variables' included, at m_k..m_k + ncols - 1),
+    ``duals`` [Rmax - 1], ``objective`` (on the widened ``function``), ``basis`` [Rmax - 1],
+    ``nonbasis`` [ldb + K - 1] and with ``ranging`` the four range arrays.  The labels are in the
+    widened LP's coding: a new variable's code is m_k + c, slack i's is m_k + ncols + i.
+
+    ``warm_rule`` is the selection rule of the WARM solve only (``"reference"`` or ``"dual"``; any
+    other value raises ValueError before the device is asked for); ``base`` does not depend on it.
+    A new variable leaves every constant as it was, so after a base run that ended at an optimum
+    the widened table is primal feasible and the default rule carries on as an ordinary primal
+    simplex.  Read ``status`` all the same; SMX_PIVOT there means ``warm_pivots`` was reached."""
+    _kernel_name(kernel)
+    wcode = _lib.rule_code(warm_rule)
+    cols = np.ascontiguousarray(cols, dtype=np.float64)
+    ncols = np.ascontiguousarray(ncols, dtype=np.int32)
+    tabs, dims, (B, Rmax, ldb) = _launch_arrays(tabs, dims)
+    if cols.ndim != 4 or cols.shape[0] != B or cols.shape[3] != Rmax:
+        raise ValueError("cols must be float64 [B][S][K][Rmax]")
+    S, K = cols.shape[1], cols.shape[2]
+    if ncols.shape != (B, S):
+        raise ValueError("ncols must be int32 [B][S]")
+    if ((ncols < 0) | (ncols > K)).any():
+        raise ValueError("ncols must lie in 0..K")
+    if B and S and ((dims[:, 2] < dims[:, 1]) & (ncols > 0).any(axis=1)).any():
+        raise ValueError("a problem whose function is shorter than m takes no new variables")
+    _need_device()
+    ldb_out = ldb + K
+    which = _launch_tier(dims, (B, Rmax, ldb), kernel)
+    warm = warm_kernel(which, Rmax, ldb_out) if B else "wave"
+    if solution_lds_bytes(Rmax, ldb_out) < 0 or not cols_fits(Rmax, ldb_out):
+        raise ValueError(ENVELOPE_ERROR)
+    if ranging and not ranging_fits(Rmax, ldb_out):
+        raise ValueError(ENVELOPE_ERROR)
+    P = int(max_pivots)
+    Pw = P if warm_pivots is None else int(warm_pivots)
+    L = _lib.load()
+    dev = torch.device(device if device is not None else "cuda")
+    with torch.cuda.device(dev):
+        d_cols = torch.from_numpy(cols).to(dev)
+        d_nc = torch.from_numpy(ncols).to(dev)
+
+    def make(stream, s0, c, d_final, d_dims, d_func, d_basis, d_nonbasis):
+        Q = B * c
+        d_tv = torch.empty((Q, Rmax, ldb_out), dtype=torch.float64, device=dev)
+        d_fv = torch.empty((Q, ldb_out), dtype=torch.float64, device=dev)
+        d_dv = torch.empty((Q, 3), dtype=torch.int32, device=dev)
+        d_bv = torch.empty((Q, Rmax), dtype=torch.int32, device=dev)
+        d_nv = torch.empty((Q, ldb_out), dtype=torch.int32, device=dev)
+        d_cs = d_cols[:, s0:s0 + c].contiguous()             # named: alive until the launch
+        d_ns = d_nc[:, s0:s0 + c].contiguous()
+        _lib.check(L.smx_batch_cols(
+            d_final.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, d_basis.data_ptr(),
+            d_nonbasis.data_ptr(), d_func.data_ptr(), d_cs.data_ptr() if K else None,
+            d_ns.data_ptr(), K, ldb_out, d_tv.data_ptr(), d_fv.data_ptr(), d_dv.data_ptr(),
+            d_bv.data_ptr(), d_nv.data_ptr(), stream.cuda_stream), "smx_batch_cols")
+        # every table's own start labels (group 1), in the widened LP's coding
+        return d_tv, d_dv, d_fv, (d_bv, d_nv, 1)
+
+    return _warm_chain(L, dev, tabs, dims, which, P, S, make, Rmax, warm, Pw, ranging, log,
+                       wcode, cols=ldb_out)
+
+
+def _widened(cons, func, columns):
+    """The ORIGINAL problem with a column set's variables inserted: the coefficients before every
+    constraint's constant, the costs into ``function`` at position m."""
+    m = len(cons[0]) - 1
+    cons = [list(r[:m]) + [float(a[i]) for a in columns] + list(r[m:]) for i, r in enumerate(cons)]
+    func = list(func[:m]) + [float(a[-1]) for a in columns] + list(func[m:])
+    return cons, func
+
+
+def solve_batch_columns(problems, columns, max_pivots: int = 256, warm_pivots=None,
+                        cold_fallback: bool = True, device=None, kernel: str = "auto",
+                        warm_rule: str = "reference"):
+    """Solve every ``(constraints, function)`` and, for each of its column sets, the problem with
+    that set's variables added; ``columns[k]`` is a list of column sets of problem k, each a list
+    of new variables ([n coefficients, cost]: the variable's coefficient in every constraint, then
+    its entry in ``function``; an empty set adds nothing).  Returns per problem ``(Solution,
+    [Scenario])``: the base answer as ``solve_batch_solutions`` gives it and one ``Scenario`` per
+    column set, in order, whose ``Solution`` has m + K' entries of ``x`` and column labels in the
+    widened LP's coding (a new variable's code is m + c, slack i's is m + K' + i).
+
+    Routing and launch grouping are ``solve_batch_solutions``'s; inside a launch the set counts
+    and sizes are padded with empty sets and dropped again (``solve_batch_columns_arrays``).
+    Problems routed ``"single"``, and those of a launch whose widened tables leave every batch
+    kernel's envelope, go through ``SimplexMethod.add_variables``.  A warm run is capped at
+    ``warm_pivots`` (default ``max_pivots``); with ``cold_fallback`` every set whose warm run did
+    not end at ``"optimum"`` is solved cold from the widened original through
+    ``solve_batch_solutions`` with the full ``max_pivots`` and marked ``warm=False``.
+    ``warm_rule`` (``"reference"`` / ``"dual"``, as in ``solve_batch_columns_arrays``) is the rule
+    of the warm solves only -- the base solves and the cold re-solves keep the reference rule."""
+    problems = list(problems)
+    columns = [[[list(a) for a in cols] for cols in sets] for sets in columns]
+    _kernel_name(kernel)                                     # refused before the columns are
+    _lib.rule_code(warm_rule)
+    if len(columns) != len(problems):
+        raise ValueError("columns must hold one list of column sets per problem")
+    for (c, _), sets in zip(problems, columns):
+        if any(len(a) != len(c) + 1 for cols in sets for a in cols):
+            raise ValueError("a new variable must hold one coefficient per constraint and a cost")
+    P = int(max_pivots)
+    Pw = P if warm_pivots is None else int(warm_pivots)
+    results = [None] * len(problems)
+
+    def single(k, c, f):
+        results[k] = _fallback_warm(c, f, columns[k], P, Pw, SimplexMethod.add_variables,
+                                    warm_rule)
+
+    def launch(which, idx, tabs, dims):
+        _, Rmax, ldb = tabs.shape
+        S = max(len(columns[k]) for k in idx)
+        K = max((len(cols) for k in idx for cols in columns[k]), default=0)
+        try:
+            warm_kernel(which, Rmax, ldb + K)
+        except ValueError:
+            for k in idx:
+                single(k, *problems[k])
+            return
+        a = np.zeros((len(idx), S, K, Rmax), dtype=np.float64)
+        nc = np.zeros((len(idx), S), dtype=np.int32)
+        for q, k in enumerate(idx):
+            n = int(dims[q, 0])
+            for s, cols in enumerate(columns[k]):
+                nc[q, s] = len(cols)
+                if cols:
+                    a[q, s, :len(cols), :n + 1] = np.asarray(cols, dtype=np.float64)
+        out = solve_batch_columns_arrays(tabs, dims, a, nc, P, Pw, device, kernel=which,
+                                         warm_rule=warm_rule)
+        for q, k in enumerate(idx):
+            results[k] = _warm_answers(out, q, int(dims[q, 0]), int(dims[q, 1]),
+                                       [len(cols) for cols in columns[k]], Pw, wide=True)
+
+    _drive(problems, kernel, max_pivots, False, single, launch)
+    if cold_fallback:
+        _cold_tail(results, lambda k, s: _widened(*problems[k], columns[k][s]), max_pivots,
+                   device, kernel)
     return results
 
 

@@ -457,23 +457,26 @@ class SimplexMethod:
         T[n, :len(frow)] = frow
         return T
 
-    def _successor(self, table, n, function, row, column, invalid_index):
+    def _successor(self, table, n, function, row, column, invalid_index, m=None, flen=None):
         """A new object on this one's backend around ``table`` ((n + 1) x (m + 1), already under
-        the labels ``row`` / ``column``): past its first pivot, with an empty pivot log."""
+        the labels ``row`` / ``column``): past its first pivot, with an empty pivot log.  ``m`` and
+        ``flen`` default to this object's."""
+        m = self.m if m is None else m
+        flen = self.flen if flen is None else flen
         new = type(self).__new__(type(self))
-        new.n, new.m, new.flen = n, self.m, self.flen
+        new.n, new.m, new.flen = n, m, flen
         new.invalid_index = invalid_index
         new.function = function
         new.row, new.column = row, column
         new._initial = None
         old = self._dev
         if self.backend == "host":
-            new._dev = type(old)(table, n, self.m, self.flen)
+            new._dev = type(old)(table, n, m, flen)
         elif self.backend == "sharded":
-            new._dev = type(old)(table, n, self.m, self.flen, old.devices, pivots=old.P,
+            new._dev = type(old)(table, n, m, flen, old.devices, pivots=old.P,
                                  exchange=old.exchange)
         else:
-            new._dev = type(old)(table, n, self.m, self.flen, device=old.device)
+            new._dev = type(old)(table, n, m, flen, device=old.device)
         new._pristine = False
         new._int0 = new._int_hist = None
         new.pivot_log = []
@@ -594,6 +597,47 @@ class SimplexMethod:
                   + list(self.column[n:]))
         return self._successor(E, n + K, list(self.function), list(self.row), column,
                                1 + max(n + K, m))
+
+    def add_variables(self, cols) -> "SimplexMethod":
+        """A new ``SimplexMethod`` on the widened table of the current one: every entry of
+        ``cols`` ([n coefficients, cost]: the new variable's coefficient in every constraint of
+        the ORIGINAL problem, then its entry in ``function``) becomes one more column under the
+        labels this table stands under, the '-b' column moves to their right.  The labels come
+        from ``row`` / ``column``, the table from the backend's ``download()`` (the caller's own
+        lists before the first pivot), the rule from ``smx_host_cols`` (include/smx.h) -- on every
+        backend, so this is correct everywhere and fast nowhere special.  The result lives on the
+        same backend and has ``m + K`` variables: ``row`` is extended by 'x{m+1}'.. before '-b',
+        ``function`` holds the costs inserted at position m, a slack keeps its name (its code
+        moves up by K), its pivot log starts empty, and ``solve()``, ``solution()`` and
+        ``ranging()`` carry on from there.  A new variable leaves every constant as it was, so
+        after a solve that ended at ``"optimum"`` the widened table is primal feasible and the
+        default rule carries on as an ordinary primal simplex; cap the run with ``max_pivots``
+        and read ``status`` all the same."""
+        n, m = self.n, self.m
+        cols = [list(a) for a in cols]
+        if any(len(a) != n + 1 for a in cols):
+            raise ValueError(f"a new variable must hold {n} coefficients and a cost")
+        if self.flen < m:        # a short f-row: its padding entries would become live costs
+            raise ValueError("a problem whose function is shorter than m takes no new variables")
+        K = len(cols)
+        A = np.ascontiguousarray(cols, dtype=np.float64).reshape(K, n + 1)
+        basis, nonbasis = self._label_codes()
+        T = self._dense_table()
+        W = np.empty((n + 1, m + K + 1), dtype=np.float64)
+        basis_out = np.empty(n, dtype=np.int32)
+        nonbasis_out = np.empty(m + K, dtype=np.int32)
+        err = _lib.load().smx_host_cols(
+            T.ctypes.data, T.shape[1], n, m, basis.ctypes.data, nonbasis.ctypes.data,
+            A.ctypes.data if K else None, K, W.ctypes.data, W.shape[1], basis_out.ctypes.data,
+            nonbasis_out.ctypes.data)
+        if err:
+            raise RuntimeError(f"smx_host_cols refused n={n}, m={m}, K={K} ({err})")
+        row = (list(self.row[:m]) + ['x' + str(m + c + 1) for c in range(K)]
+               + list(self.row[m:]))
+        function = (list(self.function[:m]) + [float(a[n]) for a in cols]
+                    + list(self.function[m:]))
+        return self._successor(W, n, function, row, list(self.column), 1 + max(n, m + K),
+                               m=m + K, flen=self.flen + K)
 
     # ---------------------------------------------------------------- the hot path -------
     def _rule_twin(self):
