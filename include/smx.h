@@ -249,8 +249,9 @@ int smx_tune_batch_gm(int32_t block, int32_t mirrors, int32_t unroll);
  *
  * smx_batch_solve_rule, smx_batch_solve_wg_rule and smx_batch_solve_gm_rule are smx_batch_solve,
  * smx_batch_solve_wg and smx_batch_solve_gm with `rule` before `stream`: SMX_RULE_REFERENCE
- * launches the very kernel of the call without a rule, SMX_RULE_DUAL its dual twin (same envelope,
- * same LDS, same workgroup size; smx_batch_solve_gm_rule honours smx_tune_batch_gm), any other
+ * launches the very kernel of the call without a rule, SMX_RULE_DUAL the same kernel instantiated
+ * for the dual rule (same envelope, same LDS, same workgroup size; smx_batch_solve_gm_rule
+ * honours smx_tune_batch_gm), any other
  * value returns hipErrorInvalidValue (1) before any HIP call.  Every other refusal and the B == 0
  * answer are those of the call without a rule. */
 #define SMX_RULE_REFERENCE 0

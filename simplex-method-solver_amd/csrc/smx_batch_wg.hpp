@@ -63,7 +63,7 @@ __device__ __forceinline__ bool wg_lp(const int32_t* __restrict__ dims, int B, i
 // rc, xv, snap (row pitch ldb, tab_elems per step; may be null) are this LP's outputs, and
 // status_out / np_out its two result words.
 //
-// Per step the decision is k_batch's (smx_batch.hpp:64-111), each candidate set reduced over the
+// Per step the decision is k_batch's (smx_batch.hpp), each candidate set reduced over the
 // workgroup: wave reduction, per-wave partials in LDS, one barrier, and the partials merged by a
 // wave.  Every wave runs that merge on the same partials, so every thread holds (status, r, c)
 // read from LDS, the loop exit is uniform and no second barrier is needed to broadcast it.
@@ -93,7 +93,7 @@ __device__ __forceinline__ bool wg_lp(const int32_t* __restrict__ dims, int B, i
 // scope; T is a plain pointer (no const __restrict__), so no load is hoisted over a barrier or
 // served from a read-only path.  An LP never spans workgroups: no flags, no spinning, no
 // co-residency.
-template <int U, bool MIRRORS, bool STASH, int RULE = SMX_RULE_REFERENCE>
+template <int U, bool MIRRORS, bool STASH, int RULE>
 __device__ __forceinline__ void wg_pivot_loop(
     double* T, int ld, double* s_prow, double* s_pcol, double* s_frow, double* s_bcol,
     const WgLp lp, const WgWalk w0, int max_pivots, int32_t* __restrict__ rc,
@@ -307,7 +307,8 @@ __device__ __forceinline__ void wg_pivot_loop(
 // wg_pivot_loop runs on it in one launch, and the final table goes to out.
 //
 // Dynamic LDS: s_T[Rmax * ldl], s_prow[ldb], s_pcol[Rmax] -- wg_lds_bytes() on the host is the
-// only place that sizes it.
+// only place that sizes it.  RULE is wg_pivot_loop's.
+template <int RULE>
 __global__ __launch_bounds__(kWgMaxBlock) void k_batch_wg(
     const double* __restrict__ tabs, const int32_t* __restrict__ dims, int B, int Rmax, int ldb,
     int ldl, int max_pivots, double* __restrict__ out, int32_t* __restrict__ rc,
@@ -327,37 +328,7 @@ __global__ __launch_bounds__(kWgMaxBlock) void k_batch_wg(
     const double* src = tabs + (size_t)b * tab_elems;
     for (WgWalk w = w0; w.i < R; w.next()) s_T[w.i * ldl + w.j] = src[w.i * ldb + w.j];
     __syncthreads();
-    wg_pivot_loop<1, false, false>(s_T, ldl, s_prow, s_pcol, nullptr, nullptr, lp, w0, max_pivots,
-                                   rc + 2 * hs, xv + 2 * hs,
-                                   snaps ? snaps + hs * tab_elems : nullptr, ldb, tab_elems,
-                                   status_out + b, np_out + b);
-    double* dst = out + (size_t)b * tab_elems;
-    for (WgWalk w = w0; w.i < R; w.next()) dst[w.i * ldb + w.j] = s_T[w.i * ldl + w.j];
-}
-
-// k_batch_wg_dual: k_batch_wg under SMX_RULE_DUAL -- the same arguments, LDS and envelope; only
-// wg_pivot_loop's rule differs.  (k_batch_wg keeps its own text: through a shared wrapper its
-// instruction stream changes.)
-__global__ __launch_bounds__(kWgMaxBlock) void k_batch_wg_dual(
-    const double* __restrict__ tabs, const int32_t* __restrict__ dims, int B, int Rmax, int ldb,
-    int ldl, int max_pivots, double* __restrict__ out, int32_t* __restrict__ rc,
-    double* __restrict__ xv, double* __restrict__ snaps, int32_t* __restrict__ status_out,
-    int32_t* __restrict__ np_out) {
-    extern __shared__ double s_wg[];   // s_T[Rmax * ldl], s_prow[ldb], s_pcol[Rmax]
-    double* s_T = s_wg;
-    double* s_prow = s_T + (size_t)Rmax * ldl;
-    double* s_pcol = s_prow + ldb;
-    WgLp lp;
-    if (!wg_lp(dims, B, Rmax, ldb, status_out, np_out, lp)) return;
-    const int b = blockIdx.x;
-    const int R = lp.n + 1;
-    const size_t tab_elems = (size_t)Rmax * ldb;
-    const size_t hs = (size_t)b * max_pivots;
-    const WgWalk w0(threadIdx.x, blockDim.x, lp.m + 1);
-    const double* src = tabs + (size_t)b * tab_elems;
-    for (WgWalk w = w0; w.i < R; w.next()) s_T[w.i * ldl + w.j] = src[w.i * ldb + w.j];
-    __syncthreads();
-    wg_pivot_loop<1, false, false, SMX_RULE_DUAL>(
+    wg_pivot_loop<1, false, false, RULE>(
         s_T, ldl, s_prow, s_pcol, nullptr, nullptr, lp, w0, max_pivots, rc + 2 * hs, xv + 2 * hs,
         snaps ? snaps + hs * tab_elems : nullptr, ldb, tab_elems, status_out + b, np_out + b);
     double* dst = out + (size_t)b * tab_elems;

@@ -1,7 +1,8 @@
 // smx_cuts.hpp -- new constraints on a solved LP: the table a warm re-solve starts from when rows
 // are added to the original problem.  k_batch_cuts (one workgroup per cut set, after
-// k_batch_solution) and host_cuts (one table on the host) share the two helpers below, so the
-// arithmetic is stated once.
+// k_batch_solution) and host_cuts (one table on the host) form every sum with scn_delta and
+// scn_cost_term of smx_scenario.hpp, so the arithmetic is stated once: a cut row is step 1 of a
+// scenario whose "costs" are the cut's coefficients.
 // Part of libsmx (compiled as one translation unit by smx_kernels.hip; not a standalone header).
 //
 // The contract (include/smx.h).  T is a final table ([n+1][m+1], f-row = row n, "-b" =
@@ -22,15 +23,6 @@ namespace {
 constexpr int kCutBlock = 256;
 constexpr int kCutWaves = kCutBlock / kWave;
 constexpr int kCutPass = 4;               // cuts whose sums one walk over T's rows feeds
-
-// The coefficient of the cut `g` on the variable the label `code` names, else +0.0: nothing there.
-__host__ __device__ __forceinline__ double cut_coef(int code, int m, const double* g) {
-    return (code >= 0 && code < m) ? g[code] : 0.0;
-}
-// one row of the sum: v + gk * t (a coefficient equal to zero is skipped, a NaN one applied)
-__host__ __device__ __forceinline__ double cut_term(double v, double gk, double t) {
-    return gk != 0.0 ? v + gk * t : v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // k_batch_cuts: one 256-thread workgroup per cut set q = b * S + s (grid = B * S), after
@@ -104,7 +96,7 @@ __global__ __launch_bounds__(kCutBlock) void k_batch_cuts(
 #pragma unroll
         for (int c = 0; c < kCutPass; ++c) {
             const double* g = G + (size_t)(c0 + (c < cnt ? c : 0)) * ldb;
-            v[c] = j == m ? g[m] : cut_coef(code, m, g);
+            v[c] = j == m ? g[m] : scn_delta(code, 0, m, g);
         }
         // a tile wholly past column m has nothing to sum
         const int rows = j0 <= m ? n : 0;
@@ -114,7 +106,7 @@ __global__ __launch_bounds__(kCutBlock) void k_batch_cuts(
             unsigned long long mask[kCutPass], any = 0ull;
 #pragma unroll
             for (int c = 0; c < kCutPass; ++c) {
-                gk[c] = c < cnt ? cut_coef(lab, m, G + (size_t)(c0 + c) * ldb) : 0.0;
+                gk[c] = c < cnt ? scn_delta(lab, 0, m, G + (size_t)(c0 + c) * ldb) : 0.0;
                 mask[c] = __ballot(gk[c] != 0.0);
                 any |= mask[c];
             }
@@ -124,7 +116,8 @@ __global__ __launch_bounds__(kCutBlock) void k_batch_cuts(
                 const double t = on ? T[(size_t)(p0 + l) * ldb + j] : 0.0;
 #pragma unroll
                 for (int c = 0; c < kCutPass; ++c)
-                    if ((mask[c] >> l) & 1ull) v[c] = cut_term(v[c], readlane_d(gk[c], l), t);
+                    if ((mask[c] >> l) & 1ull)
+                        v[c] = scn_cost_term(v[c], readlane_d(gk[c], l), t);
             }
         }
         if (j < ldb) {
@@ -149,9 +142,9 @@ void host_cuts(const double* T, int64_t ld, int n, int m, const int32_t* basis,
         const double* g = G + (int64_t)c * (m + 1);
         double* row = E + (int64_t)(n + c) * ld_out;
         for (int j = 0; j <= m; ++j) {
-            double v = j == m ? g[m] : cut_coef(nonbasis[j], m, g);
+            double v = j == m ? g[m] : scn_delta(nonbasis[j], 0, m, g);
             for (int p = 0; p < n; ++p)
-                v = cut_term(v, cut_coef(basis[p], m, g), T[(int64_t)p * ld + j]);
+                v = scn_cost_term(v, scn_delta(basis[p], 0, m, g), T[(int64_t)p * ld + j]);
             row[j] = v;
         }
         basis_out[n + c] = m + n + c;

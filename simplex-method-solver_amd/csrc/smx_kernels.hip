@@ -1158,41 +1158,51 @@ int smx_shard_update(const double* Tin, double* Tout, const double* recv, int32_
 }
 
 
-int smx_batch_solve(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
-                    int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
-                    double* snaps, int32_t* status, int32_t* npivots, void* stream) {
+// ---- the three batch tiers: one host body per tier, templated on the rule ---------------------
+// Each holds its tier's argument check, the B == 0 answer, the LDS-limit raise and the launch.
+// The entry without a rule is the SMX_RULE_REFERENCE instantiation; a *_rule entry maps its rule
+// to an instantiation through a BatchSolve pointer and refuses any other value before any HIP call.
+// (extern "C++": a template cannot have the C linkage of the block these entry points sit in.)
+namespace {
+
+using BatchSolve = int(const double*, const int32_t*, int32_t, int32_t, int32_t, int32_t, double*,
+                       int32_t*, double*, double*, int32_t*, int32_t*, void*);
+
+extern "C++" template <int RULE>
+int batch_solve(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax, int32_t ldb,
+                int32_t max_pivots, double* out, int32_t* rc, double* xv, double* snaps,
+                int32_t* status, int32_t* npivots, void* stream) {
     if (B < 0 || Rmax < 1 || Rmax > kWave || ldb < 1 || ldb > 64 || max_pivots < 0)
         return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
-    // k_batch<CMAX>: the smallest instantiation whose CMAX holds ldb
+    // k_batch<CMAX, RULE>: the smallest instantiation whose CMAX holds ldb
     using BatchFn = void (*)(const double*, const int32_t*, int, int, int, int, double*, int32_t*,
                              double*, double*, int32_t*, int32_t*);
-    const BatchFn fn = ldb <= 4 ? k_batch<4> : ldb <= 8 ? k_batch<8> : ldb <= 16 ? k_batch<16>
-                       : ldb <= 32 ? k_batch<32> : k_batch<64>;
+    const BatchFn fn = ldb <= 4 ? k_batch<4, RULE> : ldb <= 8 ? k_batch<8, RULE>
+                       : ldb <= 16 ? k_batch<16, RULE> : ldb <= 32 ? k_batch<32, RULE>
+                                                                   : k_batch<64, RULE>;
     hipLaunchKernelGGL(fn, dim3((B + 3) / 4), dim3(256), 0, S(stream), tabs, dims, B, Rmax, ldb,
                        max_pivots, out, rc, xv, snaps, status, npivots);
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+int smx_batch_solve(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
+                    int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
+                    double* snaps, int32_t* status, int32_t* npivots, void* stream) {
+    return batch_solve<SMX_RULE_REFERENCE>(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv, snaps,
+                                           status, npivots, stream);
 }
 
 int smx_batch_solve_rule(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
                          int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
                          double* snaps, int32_t* status, int32_t* npivots, int32_t rule,
                          void* stream) {
-    if (rule == SMX_RULE_REFERENCE)
-        return smx_batch_solve(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv, snaps, status,
-                               npivots, stream);
-    if (rule != SMX_RULE_DUAL) return (int)hipErrorInvalidValue;
-    if (B < 0 || Rmax < 1 || Rmax > kWave || ldb < 1 || ldb > 64 || max_pivots < 0)
-        return (int)hipErrorInvalidValue;
-    if (B == 0) return 0;
-    using BatchFn = void (*)(const double*, const int32_t*, int, int, int, int, double*, int32_t*,
-                             double*, double*, int32_t*, int32_t*);
-    const BatchFn fn = ldb <= 4 ? k_batch_dual<4> : ldb <= 8 ? k_batch_dual<8>
-                       : ldb <= 16 ? k_batch_dual<16> : ldb <= 32 ? k_batch_dual<32>
-                                                                  : k_batch_dual<64>;
-    hipLaunchKernelGGL(fn, dim3((B + 3) / 4), dim3(256), 0, S(stream), tabs, dims, B, Rmax, ldb,
-                       max_pivots, out, rc, xv, snaps, status, npivots);
-    return (int)hipGetLastError();
+    BatchSolve* const solve = rule == SMX_RULE_REFERENCE ? batch_solve<SMX_RULE_REFERENCE>
+                              : rule == SMX_RULE_DUAL    ? batch_solve<SMX_RULE_DUAL> : nullptr;
+    if (!solve) return (int)hipErrorInvalidValue;
+    return solve(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv, snaps, status, npivots, stream);
 }
 
 // ---- batched mid-sized LPs (smx_batch_wg.hpp) ------------------------------------------------
@@ -1226,6 +1236,20 @@ inline int wg_block(int64_t Rmax, int64_t ldb) {
     return t;
 }
 
+extern "C++" template <int RULE>
+int batch_solve_wg(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax, int32_t ldb,
+                   int32_t max_pivots, double* out, int32_t* rc, double* xv, double* snaps,
+                   int32_t* status, int32_t* npivots, void* stream) {
+    const int64_t lds = wg_lds_bytes(Rmax, ldb);
+    if (!wg_args_ok(B, max_pivots) || lds < 0) return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    if (const int err = wg_raise_lds_limit<k_batch_wg<RULE>>((int)kWgLdsMax)) return err;
+    hipLaunchKernelGGL(k_batch_wg<RULE>, dim3(B), dim3(wg_block(Rmax, ldb)), (size_t)lds,
+                       S(stream), tabs, dims, B, Rmax, ldb, (int)wg_ldl(ldb), max_pivots, out, rc,
+                       xv, snaps, status, npivots);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 int64_t smx_batch_wg_lds_bytes(int32_t Rmax, int32_t ldb) { return wg_lds_bytes(Rmax, ldb); }
@@ -1233,32 +1257,18 @@ int64_t smx_batch_wg_lds_bytes(int32_t Rmax, int32_t ldb) { return wg_lds_bytes(
 int smx_batch_solve_wg(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
                        int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
                        double* snaps, int32_t* status, int32_t* npivots, void* stream) {
-    const int64_t lds = wg_lds_bytes(Rmax, ldb);
-    if (!wg_args_ok(B, max_pivots) || lds < 0) return (int)hipErrorInvalidValue;
-    if (B == 0) return 0;
-    if (const int err = wg_raise_lds_limit<k_batch_wg>((int)kWgLdsMax)) return err;
-    hipLaunchKernelGGL(k_batch_wg, dim3(B), dim3(wg_block(Rmax, ldb)), (size_t)lds, S(stream),
-                       tabs, dims, B, Rmax, ldb, (int)wg_ldl(ldb), max_pivots, out, rc, xv, snaps,
-                       status, npivots);
-    return (int)hipGetLastError();
+    return batch_solve_wg<SMX_RULE_REFERENCE>(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv,
+                                              snaps, status, npivots, stream);
 }
 
 int smx_batch_solve_wg_rule(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
                             int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
                             double* snaps, int32_t* status, int32_t* npivots, int32_t rule,
                             void* stream) {
-    if (rule == SMX_RULE_REFERENCE)
-        return smx_batch_solve_wg(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv, snaps, status,
-                                  npivots, stream);
-    if (rule != SMX_RULE_DUAL) return (int)hipErrorInvalidValue;
-    const int64_t lds = wg_lds_bytes(Rmax, ldb);
-    if (!wg_args_ok(B, max_pivots) || lds < 0) return (int)hipErrorInvalidValue;
-    if (B == 0) return 0;
-    if (const int err = wg_raise_lds_limit<k_batch_wg_dual>((int)kWgLdsMax)) return err;
-    hipLaunchKernelGGL(k_batch_wg_dual, dim3(B), dim3(wg_block(Rmax, ldb)), (size_t)lds, S(stream),
-                       tabs, dims, B, Rmax, ldb, (int)wg_ldl(ldb), max_pivots, out, rc, xv, snaps,
-                       status, npivots);
-    return (int)hipGetLastError();
+    BatchSolve* const solve = rule == SMX_RULE_REFERENCE ? batch_solve_wg<SMX_RULE_REFERENCE>
+                              : rule == SMX_RULE_DUAL    ? batch_solve_wg<SMX_RULE_DUAL> : nullptr;
+    if (!solve) return (int)hipErrorInvalidValue;
+    return solve(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv, snaps, status, npivots, stream);
 }
 
 
@@ -1281,6 +1291,25 @@ int g_gm_block = 1024;   // smx_tune_batch_gm
 int g_gm_mirrors = 0;
 int g_gm_unroll = 8;
 
+extern "C++" template <int RULE>
+int batch_solve_gm(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax, int32_t ldb,
+                   int32_t max_pivots, double* out, int32_t* rc, double* xv, double* snaps,
+                   int32_t* status, int32_t* npivots, void* stream) {
+    if (!wg_args_ok(B, max_pivots) || !gm_fits(Rmax, ldb)) return (int)hipErrorInvalidValue;
+    if (B == 0) return 0;
+    GmLaunch* launch;
+    if (g_gm_mirrors)
+        launch = g_gm_unroll == 8   ? launch_batch_gm<true, 8, RULE>
+                 : g_gm_unroll == 4 ? launch_batch_gm<true, 4, RULE>
+                                    : launch_batch_gm<true, 1, RULE>;
+    else
+        launch = g_gm_unroll == 8   ? launch_batch_gm<false, 8, RULE>
+                 : g_gm_unroll == 4 ? launch_batch_gm<false, 4, RULE>
+                                    : launch_batch_gm<false, 1, RULE>;
+    return launch(g_gm_block, (int)(16 * kGmMaxSum), tabs, dims, B, Rmax, ldb, max_pivots, out, rc,
+                  xv, snaps, status, npivots, S(stream));
+}
+
 }  // namespace
 
 int smx_batch_gm_fits(int32_t Rmax, int32_t ldb) { return gm_fits(Rmax, ldb) ? 1 : 0; }
@@ -1296,39 +1325,18 @@ int smx_tune_batch_gm(int32_t block, int32_t mirrors, int32_t unroll) {
 int smx_batch_solve_gm(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
                        int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
                        double* snaps, int32_t* status, int32_t* npivots, void* stream) {
-    if (!wg_args_ok(B, max_pivots) || !gm_fits(Rmax, ldb)) return (int)hipErrorInvalidValue;
-    if (B == 0) return 0;
-    GmLaunch* launch;
-    if (g_gm_mirrors)
-        launch = g_gm_unroll == 8 ? launch_batch_gm<true, 8>
-                 : g_gm_unroll == 4 ? launch_batch_gm<true, 4> : launch_batch_gm<true, 1>;
-    else
-        launch = g_gm_unroll == 8 ? launch_batch_gm<false, 8>
-                 : g_gm_unroll == 4 ? launch_batch_gm<false, 4> : launch_batch_gm<false, 1>;
-    return launch(g_gm_block, (int)(16 * kGmMaxSum), tabs, dims, B, Rmax, ldb, max_pivots, out, rc,
-                  xv, snaps, status, npivots, S(stream));
+    return batch_solve_gm<SMX_RULE_REFERENCE>(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv,
+                                              snaps, status, npivots, stream);
 }
 
 int smx_batch_solve_gm_rule(const double* tabs, const int32_t* dims, int32_t B, int32_t Rmax,
                             int32_t ldb, int32_t max_pivots, double* out, int32_t* rc, double* xv,
                             double* snaps, int32_t* status, int32_t* npivots, int32_t rule,
                             void* stream) {
-    if (rule == SMX_RULE_REFERENCE)
-        return smx_batch_solve_gm(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv, snaps, status,
-                                  npivots, stream);
-    if (rule != SMX_RULE_DUAL) return (int)hipErrorInvalidValue;
-    if (!wg_args_ok(B, max_pivots) || !gm_fits(Rmax, ldb)) return (int)hipErrorInvalidValue;
-    if (B == 0) return 0;
-    GmLaunch* launch;
-    if (g_gm_mirrors)
-        launch = g_gm_unroll == 8 ? launch_batch_gm_dual<true, 8>
-                 : g_gm_unroll == 4 ? launch_batch_gm_dual<true, 4> : launch_batch_gm_dual<true, 1>;
-    else
-        launch = g_gm_unroll == 8 ? launch_batch_gm_dual<false, 8>
-                 : g_gm_unroll == 4 ? launch_batch_gm_dual<false, 4>
-                                    : launch_batch_gm_dual<false, 1>;
-    return launch(g_gm_block, (int)(16 * kGmMaxSum), tabs, dims, B, Rmax, ldb, max_pivots, out, rc,
-                  xv, snaps, status, npivots, S(stream));
+    BatchSolve* const solve = rule == SMX_RULE_REFERENCE ? batch_solve_gm<SMX_RULE_REFERENCE>
+                              : rule == SMX_RULE_DUAL    ? batch_solve_gm<SMX_RULE_DUAL> : nullptr;
+    if (!solve) return (int)hipErrorInvalidValue;
+    return solve(tabs, dims, B, Rmax, ldb, max_pivots, out, rc, xv, snaps, status, npivots, stream);
 }
 
 

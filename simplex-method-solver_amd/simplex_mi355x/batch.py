@@ -55,7 +55,9 @@ enqueue one kernel each on fresh outputs, ``_enqueue_base`` and ``_base_arrays``
 the warm calls share: a warm feature hands it the callable that enqueues its table-making
 kernel.  Object level: ``_drive`` routes, falls back and launches for all six ``solve_batch*``
 calls, ``_solution_at`` builds a ``Solution``, ``_status_name`` names a status, ``_warm_answers``
-and ``_cold_tail`` serve scenarios, cuts and columns alike.
+and ``_cold_tail`` serve scenarios, cuts and columns alike.  Cuts and columns, which differ in the
+axis that grows, share both levels: ``_grown_arrays`` (with ``_enqueue_cuts`` / ``_enqueue_cols``
+for the one library call each has of its own) and ``_solve_batch_grown``.
 """
 from __future__ import annotations
 
@@ -251,15 +253,15 @@ def _launch_tier(dims, shape, kernel):
 
 
 # the library's solve entry point of every tier
-_SOLVERS = {"wave": "smx_batch_solve", "workgroup": "smx_batch_solve_wg",
-            "global": "smx_batch_solve_gm"}
+_SOLVERS = {"wave": "smx_batch_solve_rule", "workgroup": "smx_batch_solve_wg_rule",
+            "global": "smx_batch_solve_gm_rule"}
 
 
 def _device_solve(L, stream, tier, d_tabs, d_dims, cap, history=False, rule=_lib.RULE_REFERENCE):
     """Enqueue the solve kernel of ``tier`` on fresh outputs, capped at ``cap`` pivots; returns
     the device tensors (final, rc, xv, status, npivots, snaps), ``snaps`` None without
-    ``history``.  ``rule`` (an SMX_RULE_* code): the reference rule goes through the entry point
-    without a rule, any other through the tier's ``_rule`` entry."""
+    ``history``.  ``rule`` is an SMX_RULE_* code for the tier's ``_rule`` entry, which under the
+    reference rule is the entry point without a rule."""
     count, rows, ldb = d_tabs.shape
     dev = d_tabs.device
     d_out = torch.empty_like(d_tabs)
@@ -273,11 +275,7 @@ def _device_solve(L, stream, tier, d_tabs, d_dims, cap, history=False, rule=_lib
     args = (d_tabs.data_ptr(), d_dims.data_ptr(), count, rows, ldb, cap, d_out.data_ptr(),
             d_rc.data_ptr(), d_xv.data_ptr(), d_snaps.data_ptr() if history else None,
             d_st.data_ptr(), d_np.data_ptr())
-    if rule == _lib.RULE_REFERENCE:
-        _lib.check(getattr(L, what)(*args, stream.cuda_stream), what)
-    else:
-        what += "_rule"
-        _lib.check(getattr(L, what)(*args, int(rule), stream.cuda_stream), what)
+    _lib.check(getattr(L, what)(*args, int(rule), stream.cuda_stream), what)
     return d_out, d_rc, d_xv, d_st, d_np, d_snaps
 
 
@@ -950,6 +948,87 @@ def warm_kernel(base: str, Rmax_out: int, ldb: int) -> str:
     raise ValueError(ENVELOPE_ERROR)
 
 
+def _enqueue_cuts(L, stream, d_final, d_dims, d_func, d_basis, d_nonbasis, d_cs, d_ns):
+    """Enqueue smx_batch_cuts for the slice ``d_cs`` [B][c][K][ldb] / ``d_ns`` [B][c] on fresh
+    outputs; returns what ``_warm_chain`` asks of its ``make``."""
+    (B, Rmax, ldb), c, K, dev = d_final.shape, d_ns.shape[1], d_cs.shape[2], d_final.device
+    d_tc = torch.empty((B * c, Rmax + K, ldb), dtype=torch.float64, device=dev)
+    d_dc = torch.empty((B * c, 3), dtype=torch.int32, device=dev)
+    d_bc = torch.empty((B * c, Rmax + K), dtype=torch.int32, device=dev)
+    _lib.check(L.smx_batch_cuts(
+        d_final.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, d_basis.data_ptr(),
+        d_nonbasis.data_ptr(), d_cs.data_ptr() if K else None, d_ns.data_ptr(), K, Rmax + K,
+        d_tc.data_ptr(), d_dc.data_ptr(), d_bc.data_ptr(), stream.cuda_stream),
+        "smx_batch_cuts")
+    # every table's own start labels (group 1): its LP's column labels and function row
+    return (d_tc, d_dc, d_func.repeat_interleave(c, dim=0),
+            (d_bc, d_nonbasis.repeat_interleave(c, dim=0), 1))
+
+
+def _enqueue_cols(L, stream, d_final, d_dims, d_func, d_basis, d_nonbasis, d_cs, d_ns):
+    """Enqueue smx_batch_cols for the slice ``d_cs`` [B][c][K][Rmax] / ``d_ns`` [B][c] on fresh
+    outputs; returns what ``_warm_chain`` asks of its ``make``."""
+    (B, Rmax, ldb), c, K, dev = d_final.shape, d_ns.shape[1], d_cs.shape[2], d_final.device
+    d_tv = torch.empty((B * c, Rmax, ldb + K), dtype=torch.float64, device=dev)
+    d_fv = torch.empty((B * c, ldb + K), dtype=torch.float64, device=dev)
+    d_dv = torch.empty((B * c, 3), dtype=torch.int32, device=dev)
+    d_bv = torch.empty((B * c, Rmax), dtype=torch.int32, device=dev)
+    d_nv = torch.empty((B * c, ldb + K), dtype=torch.int32, device=dev)
+    _lib.check(L.smx_batch_cols(
+        d_final.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, d_basis.data_ptr(),
+        d_nonbasis.data_ptr(), d_func.data_ptr(), d_cs.data_ptr() if K else None,
+        d_ns.data_ptr(), K, ldb + K, d_tv.data_ptr(), d_fv.data_ptr(), d_dv.data_ptr(),
+        d_bv.data_ptr(), d_nv.data_ptr(), stream.cuda_stream), "smx_batch_cols")
+    # every table's own start labels (group 1), in the widened LP's coding
+    return d_tv, d_dv, d_fv, (d_bv, d_nv, 1)
+
+
+def _grown_arrays(wide, tabs, dims, sets, counts, max_pivots, warm_pivots, device, kernel,
+                  ranging, log, warm_rule):
+    """``solve_batch_cuts_arrays`` (``wide`` False: K rows of ldb entries are added to every
+    table) and ``solve_batch_columns_arrays`` (``wide`` True: K columns of Rmax entries), stated
+    once: the checks in their order, the upload and the ``_warm_chain`` whose ``make`` enqueues the
+    feature's kernel (``_enqueue_cuts`` / ``_enqueue_cols``) on a slice of the sets."""
+    name, last, fits, enqueue = (("cols", "Rmax", cols_fits, _enqueue_cols) if wide else
+                                 ("cuts", "ldb", cuts_fits, _enqueue_cuts))
+    _kernel_name(kernel)
+    wcode = _lib.rule_code(warm_rule)
+    sets = np.ascontiguousarray(sets, dtype=np.float64)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    tabs, dims, (B, Rmax, ldb) = _launch_arrays(tabs, dims)
+    if sets.ndim != 4 or sets.shape[0] != B or sets.shape[3] != (Rmax if wide else ldb):
+        raise ValueError(f"{name} must be float64 [B][S][K][{last}]")
+    S, K = sets.shape[1], sets.shape[2]
+    if counts.shape != (B, S):
+        raise ValueError(f"n{name} must be int32 [B][S]")
+    if ((counts < 0) | (counts > K)).any():
+        raise ValueError(f"n{name} must lie in 0..K")
+    if wide and B and S and ((dims[:, 2] < dims[:, 1]) & (counts > 0).any(axis=1)).any():
+        raise ValueError("a problem whose function is shorter than m takes no new variables")
+    _need_device()
+    rows, width = (Rmax, ldb + K) if wide else (Rmax + K, ldb)
+    which = _launch_tier(dims, (B, Rmax, ldb), kernel)
+    warm = warm_kernel(which, rows, width) if B else "wave"
+    if solution_lds_bytes(rows, width) < 0 or not fits(rows, width):
+        raise ValueError(ENVELOPE_ERROR)
+    if ranging and not ranging_fits(rows, width):
+        raise ValueError(ENVELOPE_ERROR)
+    P = int(max_pivots)
+    Pw = P if warm_pivots is None else int(warm_pivots)
+    L = _lib.load()
+    dev = torch.device(device if device is not None else "cuda")
+    with torch.cuda.device(dev):
+        d_sets = torch.from_numpy(sets).to(dev)
+        d_counts = torch.from_numpy(counts).to(dev)
+
+    def make(stream, s0, c, *base):
+        return enqueue(L, stream, *base, d_sets[:, s0:s0 + c].contiguous(),
+                       d_counts[:, s0:s0 + c].contiguous())
+
+    return _warm_chain(L, dev, tabs, dims, which, P, S, make, rows, warm, Pw, ranging, log,
+                       wcode, cols=width if wide else None)
+
+
 def solve_batch_cuts_arrays(tabs: np.ndarray, dims: np.ndarray, cuts: np.ndarray,
                             ncuts: np.ndarray, max_pivots: int = 256, warm_pivots=None,
                             device=None, kernel: str = "auto", ranging: bool = False,
@@ -984,57 +1063,59 @@ def solve_batch_cuts_arrays(tabs: np.ndarray, dims: np.ndarray, cuts: np.ndarray
     base run that ended at an optimum it is dual feasible and under ``"dual"`` (SMX_RULE_DUAL,
     include/smx.h) the warm run terminates, up to degenerate cycling.  Either way read ``status``;
     SMX_PIVOT there means ``warm_pivots`` was reached."""
-    _kernel_name(kernel)
-    wcode = _lib.rule_code(warm_rule)
-    cuts = np.ascontiguousarray(cuts, dtype=np.float64)
-    ncuts = np.ascontiguousarray(ncuts, dtype=np.int32)
-    tabs, dims, (B, Rmax, ldb) = _launch_arrays(tabs, dims)
-    if cuts.ndim != 4 or cuts.shape[0] != B or cuts.shape[3] != ldb:
-        raise ValueError("cuts must be float64 [B][S][K][ldb]")
-    S, K = cuts.shape[1], cuts.shape[2]
-    if ncuts.shape != (B, S):
-        raise ValueError("ncuts must be int32 [B][S]")
-    if ((ncuts < 0) | (ncuts > K)).any():
-        raise ValueError("ncuts must lie in 0..K")
-    _need_device()
-    Rout = Rmax + K
-    which = _launch_tier(dims, (B, Rmax, ldb), kernel)
-    warm = warm_kernel(which, Rout, ldb) if B else "wave"
-    if solution_lds_bytes(Rout, ldb) < 0 or not cuts_fits(Rout, ldb):
-        raise ValueError(ENVELOPE_ERROR)
-    if ranging and not ranging_fits(Rout, ldb):
-        raise ValueError(ENVELOPE_ERROR)
-    P = int(max_pivots)
-    Pw = P if warm_pivots is None else int(warm_pivots)
-    L = _lib.load()
-    dev = torch.device(device if device is not None else "cuda")
-    with torch.cuda.device(dev):
-        d_cuts = torch.from_numpy(cuts).to(dev)
-        d_nc = torch.from_numpy(ncuts).to(dev)
-
-    def make(stream, s0, c, d_final, d_dims, d_func, d_basis, d_nonbasis):
-        Q = B * c
-        d_tc = torch.empty((Q, Rout, ldb), dtype=torch.float64, device=dev)
-        d_dc = torch.empty((Q, 3), dtype=torch.int32, device=dev)
-        d_bc = torch.empty((Q, Rout), dtype=torch.int32, device=dev)
-        d_cs = d_cuts[:, s0:s0 + c].contiguous()             # named: alive until the launch
-        d_ns = d_nc[:, s0:s0 + c].contiguous()
-        _lib.check(L.smx_batch_cuts(
-            d_final.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, d_basis.data_ptr(),
-            d_nonbasis.data_ptr(), d_cs.data_ptr() if K else None, d_ns.data_ptr(), K, Rout,
-            d_tc.data_ptr(), d_dc.data_ptr(), d_bc.data_ptr(), stream.cuda_stream),
-            "smx_batch_cuts")
-        # every table's own start labels (group 1): its LP's column labels and function row
-        return (d_tc, d_dc, d_func.repeat_interleave(c, dim=0),
-                (d_bc, d_nonbasis.repeat_interleave(c, dim=0), 1))
-
-    return _warm_chain(L, dev, tabs, dims, which, P, S, make, Rout, warm, Pw, ranging, log,
-                       wcode)
+    return _grown_arrays(False, tabs, dims, cuts, ncuts, max_pivots, warm_pivots, device, kernel,
+                         ranging, log, warm_rule)
 
 
 def _enlarged(cons, func, rows):
     """The ORIGINAL problem with a cut set's rows appended."""
     return [list(r) for r in cons] + [[float(v) for v in r] for r in rows], list(func)
+
+
+def _solve_batch_grown(wide, problems, sets, max_pivots, warm_pivots, cold_fallback, device, kernel,
+                       warm_rule):
+    """``solve_batch_cuts`` (``wide`` False) and ``solve_batch_columns`` (``wide`` True) once their
+    ``sets`` are checked: a launch pads its members' sets into [len(idx)][S][K][ldb or Rmax] plus
+    counts and goes through the array level, unless its grown tables leave every tier
+    (``warm_kernel``): then, like the problems routed ``"single"``, its members go one by one."""
+    arrays, successor, grown = (
+        (solve_batch_columns_arrays, SimplexMethod.add_variables, _widened) if wide else
+        (solve_batch_cuts_arrays, SimplexMethod.add_constraints, _enlarged))
+    P = int(max_pivots)
+    Pw = P if warm_pivots is None else int(warm_pivots)
+    results = [None] * len(problems)
+
+    def single(k, c, f):
+        results[k] = _fallback_warm(c, f, sets[k], P, Pw, successor, warm_rule)
+
+    def launch(which, idx, tabs, dims):
+        _, Rmax, ldb = tabs.shape
+        S = max(len(sets[k]) for k in idx)
+        K = max((len(new) for k in idx for new in sets[k]), default=0)
+        try:
+            warm_kernel(which, *((Rmax, ldb + K) if wide else (Rmax + K, ldb)))
+        except ValueError:
+            for k in idx:
+                single(k, *problems[k])
+            return
+        g = np.zeros((len(idx), S, K, Rmax if wide else ldb), dtype=np.float64)
+        nc = np.zeros((len(idx), S), dtype=np.int32)
+        for q, k in enumerate(idx):
+            used = int(dims[q, 0 if wide else 1]) + 1
+            for s, new in enumerate(sets[k]):
+                nc[q, s] = len(new)
+                if new:
+                    g[q, s, :len(new), :used] = np.asarray(new, dtype=np.float64)
+        out = arrays(tabs, dims, g, nc, P, Pw, device, kernel=which, warm_rule=warm_rule)
+        for q, k in enumerate(idx):
+            results[k] = _warm_answers(out, q, int(dims[q, 0]), int(dims[q, 1]),
+                                       [len(new) for new in sets[k]], Pw, wide)
+
+    _drive(problems, kernel, max_pivots, False, single, launch)
+    if cold_fallback:
+        _cold_tail(results, lambda k, s: grown(*problems[k], sets[k][s]), max_pivots, device,
+                   kernel)
+    return results
 
 
 def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
@@ -1066,43 +1147,8 @@ def solve_batch_cuts(problems, cuts, max_pivots: int = 256, warm_pivots=None,
     for (c, _), sets in zip(problems, cuts):
         if any(len(r) != len(c[0]) for rows in sets for r in rows):
             raise ValueError("a cut must have the length of its problem's constraints")
-    P = int(max_pivots)
-    Pw = P if warm_pivots is None else int(warm_pivots)
-    results = [None] * len(problems)
-
-    def single(k, c, f):
-        results[k] = _fallback_warm(c, f, cuts[k], P, Pw, SimplexMethod.add_constraints,
-                                    warm_rule)
-
-    def launch(which, idx, tabs, dims):
-        _, Rmax, ldb = tabs.shape
-        S = max(len(cuts[k]) for k in idx)
-        K = max((len(rows) for k in idx for rows in cuts[k]), default=0)
-        try:
-            warm_kernel(which, Rmax + K, ldb)
-        except ValueError:
-            for k in idx:
-                single(k, *problems[k])
-            return
-        g = np.zeros((len(idx), S, K, ldb), dtype=np.float64)
-        nc = np.zeros((len(idx), S), dtype=np.int32)
-        for q, k in enumerate(idx):
-            m = int(dims[q, 1])
-            for s, rows in enumerate(cuts[k]):
-                nc[q, s] = len(rows)
-                if rows:
-                    g[q, s, :len(rows), :m + 1] = np.asarray(rows, dtype=np.float64)
-        out = solve_batch_cuts_arrays(tabs, dims, g, nc, P, Pw, device, kernel=which,
-                                      warm_rule=warm_rule)
-        for q, k in enumerate(idx):
-            results[k] = _warm_answers(out, q, int(dims[q, 0]), int(dims[q, 1]),
-                                       [len(rows) for rows in cuts[k]], Pw)
-
-    _drive(problems, kernel, max_pivots, False, single, launch)
-    if cold_fallback:
-        _cold_tail(results, lambda k, s: _enlarged(*problems[k], cuts[k][s]), max_pivots, device,
-                   kernel)
-    return results
+    return _solve_batch_grown(False, problems, cuts, max_pivots, warm_pivots, cold_fallback, device,
+                              kernel, warm_rule)
 
 
 def solve_batch_columns_arrays(tabs: np.ndarray, dims: np.ndarray, cols: np.ndarray,
@@ -1139,55 +1185,8 @@ def solve_batch_columns_arrays(tabs: np.ndarray, dims: np.ndarray, cols: np.ndar
     A new variable leaves every constant as it was, so after a base run that ended at an optimum
     the widened table is primal feasible and the default rule carries on as an ordinary primal
     simplex.  Read ``status`` all the same; SMX_PIVOT there means ``warm_pivots`` was reached."""
-    _kernel_name(kernel)
-    wcode = _lib.rule_code(warm_rule)
-    cols = np.ascontiguousarray(cols, dtype=np.float64)
-    ncols = np.ascontiguousarray(ncols, dtype=np.int32)
-    tabs, dims, (B, Rmax, ldb) = _launch_arrays(tabs, dims)
-    if cols.ndim != 4 or cols.shape[0] != B or cols.shape[3] != Rmax:
-        raise ValueError("cols must be float64 [B][S][K][Rmax]")
-    S, K = cols.shape[1], cols.shape[2]
-    if ncols.shape != (B, S):
-        raise ValueError("ncols must be int32 [B][S]")
-    if ((ncols < 0) | (ncols > K)).any():
-        raise ValueError("ncols must lie in 0..K")
-    if B and S and ((dims[:, 2] < dims[:, 1]) & (ncols > 0).any(axis=1)).any():
-        raise ValueError("a problem whose function is shorter than m takes no new variables")
-    _need_device()
-    ldb_out = ldb + K
-    which = _launch_tier(dims, (B, Rmax, ldb), kernel)
-    warm = warm_kernel(which, Rmax, ldb_out) if B else "wave"
-    if solution_lds_bytes(Rmax, ldb_out) < 0 or not cols_fits(Rmax, ldb_out):
-        raise ValueError(ENVELOPE_ERROR)
-    if ranging and not ranging_fits(Rmax, ldb_out):
-        raise ValueError(ENVELOPE_ERROR)
-    P = int(max_pivots)
-    Pw = P if warm_pivots is None else int(warm_pivots)
-    L = _lib.load()
-    dev = torch.device(device if device is not None else "cuda")
-    with torch.cuda.device(dev):
-        d_cols = torch.from_numpy(cols).to(dev)
-        d_nc = torch.from_numpy(ncols).to(dev)
-
-    def make(stream, s0, c, d_final, d_dims, d_func, d_basis, d_nonbasis):
-        Q = B * c
-        d_tv = torch.empty((Q, Rmax, ldb_out), dtype=torch.float64, device=dev)
-        d_fv = torch.empty((Q, ldb_out), dtype=torch.float64, device=dev)
-        d_dv = torch.empty((Q, 3), dtype=torch.int32, device=dev)
-        d_bv = torch.empty((Q, Rmax), dtype=torch.int32, device=dev)
-        d_nv = torch.empty((Q, ldb_out), dtype=torch.int32, device=dev)
-        d_cs = d_cols[:, s0:s0 + c].contiguous()             # named: alive until the launch
-        d_ns = d_nc[:, s0:s0 + c].contiguous()
-        _lib.check(L.smx_batch_cols(
-            d_final.data_ptr(), d_dims.data_ptr(), B, c, Rmax, ldb, d_basis.data_ptr(),
-            d_nonbasis.data_ptr(), d_func.data_ptr(), d_cs.data_ptr() if K else None,
-            d_ns.data_ptr(), K, ldb_out, d_tv.data_ptr(), d_fv.data_ptr(), d_dv.data_ptr(),
-            d_bv.data_ptr(), d_nv.data_ptr(), stream.cuda_stream), "smx_batch_cols")
-        # every table's own start labels (group 1), in the widened LP's coding
-        return d_tv, d_dv, d_fv, (d_bv, d_nv, 1)
-
-    return _warm_chain(L, dev, tabs, dims, which, P, S, make, Rmax, warm, Pw, ranging, log,
-                       wcode, cols=ldb_out)
+    return _grown_arrays(True, tabs, dims, cols, ncols, max_pivots, warm_pivots, device, kernel,
+                         ranging, log, warm_rule)
 
 
 def _widened(cons, func, columns):
@@ -1228,43 +1227,8 @@ def solve_batch_columns(problems, columns, max_pivots: int = 256, warm_pivots=No
     for (c, _), sets in zip(problems, columns):
         if any(len(a) != len(c) + 1 for cols in sets for a in cols):
             raise ValueError("a new variable must hold one coefficient per constraint and a cost")
-    P = int(max_pivots)
-    Pw = P if warm_pivots is None else int(warm_pivots)
-    results = [None] * len(problems)
-
-    def single(k, c, f):
-        results[k] = _fallback_warm(c, f, columns[k], P, Pw, SimplexMethod.add_variables,
-                                    warm_rule)
-
-    def launch(which, idx, tabs, dims):
-        _, Rmax, ldb = tabs.shape
-        S = max(len(columns[k]) for k in idx)
-        K = max((len(cols) for k in idx for cols in columns[k]), default=0)
-        try:
-            warm_kernel(which, Rmax, ldb + K)
-        except ValueError:
-            for k in idx:
-                single(k, *problems[k])
-            return
-        a = np.zeros((len(idx), S, K, Rmax), dtype=np.float64)
-        nc = np.zeros((len(idx), S), dtype=np.int32)
-        for q, k in enumerate(idx):
-            n = int(dims[q, 0])
-            for s, cols in enumerate(columns[k]):
-                nc[q, s] = len(cols)
-                if cols:
-                    a[q, s, :len(cols), :n + 1] = np.asarray(cols, dtype=np.float64)
-        out = solve_batch_columns_arrays(tabs, dims, a, nc, P, Pw, device, kernel=which,
-                                         warm_rule=warm_rule)
-        for q, k in enumerate(idx):
-            results[k] = _warm_answers(out, q, int(dims[q, 0]), int(dims[q, 1]),
-                                       [len(cols) for cols in columns[k]], Pw, wide=True)
-
-    _drive(problems, kernel, max_pivots, False, single, launch)
-    if cold_fallback:
-        _cold_tail(results, lambda k, s: _widened(*problems[k], columns[k][s]), max_pivots,
-                   device, kernel)
-    return results
+    return _solve_batch_grown(True, problems, columns, max_pivots, warm_pivots, cold_fallback,
+                              device, kernel, warm_rule)
 
 
 def _table(T, n, flen, m):

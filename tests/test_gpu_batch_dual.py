@@ -271,6 +271,48 @@ def test_rule_zero_is_the_entry_without_a_rule(tier, n, m, seeds, cap):
     _same_lp(a, 0, lps[0], 24, du.REFERENCE, (tier, "reference"), exp=ref)
 
 
+_GM_CASE = {}
+
+
+def _gm_case(rule):
+    """The global tier's LPs for the knob sweep and their restated runs under `rule`, made once:
+    the ("global", 142, 142, ...) chain's warm tables and the (142, 142, 70) hand-made one-step
+    tables, all capped at 24 pivots."""
+    if not _GM_CASE:
+        _, n, m, seeds, cap = CHAINS[2]
+        _GM_CASE["chain"] = [lp_ for seed in seeds for lp_ in _warm_lps(n, m, seed, cap)]
+        n, m, nb = GLOBAL[0]
+        _GM_CASE["hand"] = [(T, n, m, flen)
+                            for _, T, _, _, flen, _, _ in du.handmade(n, m, nb, _cols(m, 0))]
+    if rule not in _GM_CASE:
+        _GM_CASE[rule] = [du.run(*lp_, 24, rule) for lp_ in _GM_CASE["chain"] + _GM_CASE["hand"]]
+    return _GM_CASE["chain"], _GM_CASE["hand"], _GM_CASE[rule]
+
+
+@pytest.mark.parametrize("mirrors,unroll", [(mi, u) for mi in (0, 1) for u in (1, 4, 8)])
+def test_every_global_knob_pair_under_both_rules(mirrors, unroll):
+    """smx_batch_solve_gm_rule picks one of twelve instantiations from (mirrors, unroll, rule):
+    each of them on one launch of the chain's warm tables and the hand-made one-step tables, at 256
+    threads (80 elements a thread: every look-ahead depth runs and leaves a tail), against the
+    restatement bit for bit."""
+    from simplex_mi355x import _lib
+    L = _lib.load()
+    _, n, m, _, _ = CHAINS[2]
+    prev = L.smx_tune_batch_gm(256, mirrors, unroll)
+    try:
+        for rule in (du.REFERENCE, du.DUAL):
+            chain, hand, exps = _gm_case(rule)
+            res = _launch("global", chain + hand, n + 2, m + 3, 24, rule)
+            assert res["err"] == 0
+            for q, (lp_, exp) in enumerate(zip(chain + hand, exps)):
+                _same_lp(res, q, lp_, 24, rule, (mirrors, unroll, rule, q), q >= len(chain), exp)
+            assert all(sum(e[2] for e in part) > 0 for part in (exps[:len(chain)], exps[len(chain):]))
+            assert (sum(e[4] for e in exps) > 0) == (rule == du.DUAL)
+    finally:
+        L.smx_tune_batch_gm(prev & 0xffff, (prev >> 16) & 0xf, prev >> 20)
+    assert L.smx_tune_batch_gm(-1, -1, -1) == prev
+
+
 def test_rule_entries_refuse():
     """Every refusal of the `_rule` entries with real device pointers: an unknown rule, a bad
     shape, a negative count or cap -- hipErrorInvalidValue, nothing launched, nothing written."""

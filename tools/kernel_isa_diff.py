@@ -9,6 +9,12 @@ directives and normalising the function number in local labels (.LBB<n>_<k> -> .
 line per kernel: `identical` or `different`, with both instruction counts (labels not counted).
 Exit status 1 if any kernel differs or is missing from one file, else 0.  --show N prints the
 first N lines of a unified diff for each kernel that differs.
+
+--rename REGEX=REPL (repeatable, applied in order with re.sub) rewrites the demangled names of the
+OLD listing before matching, and kernels are then matched by demangled name: a kernel whose symbol
+changed is reported `identical` / `different` instead of `missing`.
+
+    python tools/kernel_isa_diff.py OLD.s NEW.s . --rename 'k_batch_wg_dual[(]=k_batch_wg<1>('
 """
 import argparse
 import difflib
@@ -58,17 +64,28 @@ def count(body):
     return sum(1 for l in body if not l.endswith(":"))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("filter", help="regular expression on the kernel's name")
     ap.add_argument("--show", type=int, default=0, metavar="N",
                     help="print the first N diff lines of each kernel that differs")
-    a = ap.parse_args()
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL",
+                    help="rewrite the old listing's demangled names before matching (repeatable)")
+    a = ap.parse_args(argv)
     ko, kn = kernels(a.old), kernels(a.new)
+    if a.rename:   # match by demangled name, the old side's after the renames
+        subs = [r.split("=", 1) for r in a.rename]
+        if any(len(sub) != 2 for sub in subs):
+            ap.error("--rename takes REGEX=REPL")
+        po, pn = demangle(sorted(ko)), demangle(sorted(kn))
+        for rx, repl in subs:
+            po = {n: re.sub(rx, repl, p) for n, p in po.items()}
+        ko = {po[n]: body for n, body in ko.items()}
+        kn = {pn[n]: body for n, body in kn.items()}
     names = sorted(set(ko) | set(kn))
-    pretty = demangle(names)
+    pretty = {n: n for n in names} if a.rename else demangle(names)
     pat = re.compile(a.filter)
     names = [n for n in names if pat.search(n) or pat.search(pretty[n])]
     if not names:
