@@ -527,6 +527,97 @@ int smx_host_cols(const double* T, int64_t ld, int32_t n, int32_t m, const int32
                   const int32_t* nonbasis, const double* A, int32_t K, double* W_out,
                   int64_t ld_out, int32_t* basis_out, int32_t* nonbasis_out);
 
+/* ---- integer programs: branch and bound on solved nodes (smx_branch.hpp) ----------------------
+ * "These variables must be whole numbers."  A NODE is a table T ([n+1][m+1], f-row = row n, "-b" =
+ * column m) under the labels basis[p] / nonbasis[j] as smx_batch_solution writes them, with its
+ * dims, its LP's func row and an integrality mask ints[k], k < m (int32, non-zero: x{k+1} must be
+ * whole).  Labels are distinct; duplicates are the caller's error, as for smx_batch_solution_from.
+ *
+ * PICK.  Every row p < n with basis[p] = k, 0 <= k < m and ints[k] != 0 is examined:
+ *        v = T[p][m];  lo = floor(v);  a = v - lo;  b = (lo + 1.0) - v;  d = b < a ? b : a
+ * each a single rounded operation.  Row p is a candidate iff d > tol; a NaN or infinite v gives a
+ * NaN d and is never a candidate, a v past 2^53 gives d = 0, and tol = 0 is allowed.  The pick is
+ * the candidate with the largest d, ties to the lowest variable code k (then the lowest row p,
+ * which labels that are distinct never need).  That is a total order, so the result is one bit
+ * pattern however the rows are grouped for the reduction.  Outputs per node: bvar (k, or -1: no
+ * candidate, the node's answer is integral on the marked variables), brow (p, or -1) and bval (v,
+ * or +0.0).  A code outside 0..n+m-1 names nothing; a slack row is never examined.
+ * Beside the pick, over ALL rows p < n whatever their labels: bneg = T[nb][m] at the smallest nb
+ * with T[nb][m] < 0, the row both selection rules look at first and so the row behind a status
+ * SMX_INCORRECT, and bmin = the smallest T[p][m] that is < 0; each +0.0 where no "-b" is negative
+ * (a NaN is not).  A caller reads from them how far a node that ended at SMX_INCORRECT is from
+ * feasible: the kernels compare with zero exactly, and a constant that is zero in exact
+ * arithmetic can stand at -1e-16 after a few pivots.
+ *
+ * BRANCH.  Given a node and a row p with basis[p] = k < m and v = T[p][m], the two children are
+ * exactly the extended tables E of smx_batch_cuts (above) for one cut each:
+ *        down  g[k] = -1.0, g[m] = floor(v), all else +0.0        (-x_k + floor(v) >= 0)
+ *        up    g[k] = +1.0, g[m] = -ceil(v), all else +0.0        ( x_k - ceil(v)  >= 0)
+ * bit for bit: the cuts rule's start values, its skip of zero coefficients, its products rounded
+ * on their own and its order.  With one non-zero coefficient the new row follows without a walk
+ * over the rows, c = -1.0 / +1.0:
+ *        E[n][j] = s + c * T[p][j]   s = c where nonbasis[j] = k (never under distinct labels),
+ *                                    else +0.0, for j < m
+ *        E[n][m] = g[m] + c * v
+ * Rows 0..n-1 are T's bits, the f-row moves to row n + 1, the padding is smx_batch_cuts's.  The
+ * child's basis is the parent's with code m + n at row n, nonbasis is copied, dims becomes
+ * (n + 1, m, flen) and func is the parent's.  Both children violate their new row at the parent's
+ * answer by construction (E[n][m] < 0 for a fractional v), so a warm run has work to do; the
+ * parent's f-row is kept, so from a parent at SMX_OPTIMUM a child is dual feasible and under
+ * SMX_RULE_DUAL its run ends, up to degenerate cycling, at SMX_OPTIMUM or at SMX_INCORRECT, which
+ * from a dual-feasible table proves the child empty.  A child is a node: the chain goes on.
+ * SNAP.  The branch takes a tolerance snap >= 0: a "-b" entry v of rows 0..n-1 with
+ * -snap <= v < 0 is written to both children as +0.0 (the new row is formed from T's own bits).
+ * With snap = 0, or a NaN, nothing is snapped and a child is the cuts rule's table bit for bit.  A
+ * constant that is zero in exact arithmetic -- two branches that fix a variable -- can stand at
+ * -1e-16, and a row of it without a positive entry would end every descendant's run at once.
+ *
+ * smx_batch_branch_pick (device pointers): final fp64 [Q][Rmax][ldb], dims int32 [Q][3], basis
+ * int32 [Q][Rmax], ints int32 [B][ldb] read at row lp[q] (lp int32 [Q]: the problem a node belongs
+ * to); outputs bvar, brow int32 [Q], bval, bneg, bmin fp64 [Q].  One wavefront per node.  A node without
+ * 1 <= n < Rmax and 1 <= m < ldb, or with lp[q] outside 0..B-1, has no candidate and bneg = bmin =
+ * +0.0.  Returns
+ * hipErrorInvalidValue (1) before any HIP call for Q < 0, B < 0, a shape outside
+ * smx_batch_branch_fits or, with Q > 0, a null pointer (ints may be null when B == 0); Q == 0
+ * returns 0 without a launch. */
+int smx_batch_branch_pick(const double* final, const int32_t* dims, int32_t Q, int32_t Rmax,
+                          int32_t ldb, const int32_t* basis, const int32_t* ints, int32_t B,
+                          const int32_t* lp, double tol, int32_t* bvar, int32_t* brow,
+                          double* bval, double* bneg, double* bmin, void* stream);
+/* smx_batch_branch (device pointers): the nodes as above with nonbasis int32 [Q][ldb] and func
+ * fp64 [Q][ldb]; src int32 [Qc] lists the nodes to expand (any order, gaps and repeats allowed: a
+ * pruned node is simply not listed), brow int32 [Q] is the pick's.  Outputs, children 2i (down)
+ * and 2i + 1 (up) of parent src[i]: tabs_c fp64 [2Qc][Rmax_out][ldb], dims_c int32 [2Qc][3],
+ * basis_c int32 [2Qc][Rmax_out] and nonbasis_c int32 [2Qc][ldb] (-1 as padding), func_c fp64
+ * [2Qc][ldb]; smx_batch_solution_from(group = 1) serves the children unchanged.  One workgroup
+ * per parent reads its block once and writes it twice; every output element is written exactly
+ * once.  Rmax_out >= Rmax, so parents of any depth can share one block stride.  A parent whose
+ * brow is outside 0..n-1, whose label there is no variable or with n + 1 >= Rmax_out gives two
+ * relayouts without a new row and its dims kept; dims outside the block are handled as in
+ * smx_batch_cuts (nonbasis copied whole); a src outside 0..Q-1 names no parent and gives two blocks
+ * of +0.0 with dims (0, 0, 0), labels -1 and func +0.0.  Returns hipErrorInvalidValue (1) before
+ * any HIP call for Q < 0, Qc < 0, 2 * Qc past 2^31 - 1, Rmax_out < Rmax, (Rmax, ldb) or
+ * (Rmax_out, ldb) outside smx_batch_branch_fits or, with Qc > 0, a null pointer (the node arrays
+ * may be null when Q == 0); Qc == 0 returns 0 without a launch. */
+int smx_batch_branch(const double* final, const int32_t* dims, int32_t Q, int32_t Rmax,
+                     int32_t ldb, const int32_t* basis, const int32_t* nonbasis,
+                     const double* func, const int32_t* src, const int32_t* brow, int32_t Qc,
+                     int32_t Rmax_out, double snap, double* tabs_c, int32_t* dims_c,
+                     int32_t* basis_c, int32_t* nonbasis_c, double* func_c, void* stream);
+/* Host only: smx_batch_cuts_fits. */
+int smx_batch_branch_fits(int32_t Rmax_out, int32_t ldb);
+/* The same rules on one HOST table with leading dimension ld >= m + 1 (synchronous).  The pick:
+ * ints [m]; -1 for a null pointer, n < 1, m < 1 or ld < m + 1.  The branch on row p, through the
+ * host cuts rule itself and the snap: E_down and E_up [n+2][ld_out] (ld_out >= m + 1; columns 0..m of every
+ * row are written; neither may overlap T) and basis_out [n+1], the labels of both; -1 also for p
+ * outside 0..n-1 or a label at p that is no variable. */
+int smx_host_branch_pick(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                         const int32_t* ints, double tol, int32_t* bvar, int32_t* brow,
+                         double* bval, double* bneg, double* bmin);
+int smx_host_branch(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                    const int32_t* nonbasis, int32_t p, double snap, double* E_down,
+                    double* E_up, int64_t ld_out, int32_t* basis_out);
+
 /* ---- row-sharded engine (one process per GPU; exchange = caller's all-gather) ----------
  * Local tableau: shape->rows constraint rows (global rows row0 .. row0+rows-1) + a replica
  * of the f-row as local row `rows`.  Per pivot:

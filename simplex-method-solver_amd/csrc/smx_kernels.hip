@@ -23,6 +23,9 @@
 //   smx_cols.hpp      k_batch_cols (a batch's final tables, labels and new variables' columns ->
 //                     the widened tables warm re-solves start from, one workgroup per column set)
 //                     and host_cols
+//   smx_branch.hpp    k_batch_branch_pick (a batch of solved nodes and an integrality mask -> the
+//                     variable to branch on, one wavefront per node), k_batch_branch (the two
+//                     children's tables and labels, one workgroup per parent) and their host twins
 //   smx_resident.hpp  k_resident: the whole pivot loop in one persistent launch, tableau in LDS
 //   smx_block.hpp     k_blk_*: P pivots per HBM sweep, decisions planned from the sweep's input
 //   smx_sweep.hpp     k_blk_sweep, k_blk_sweep_rest: the sweep itself
@@ -74,6 +77,7 @@ static_assert(sizeof(smx_part) == 32, "smx_part layout");
 #include "smx_scenario.hpp"
 #include "smx_cuts.hpp"
 #include "smx_cols.hpp"
+#include "smx_branch.hpp"
 #include "smx_resident.hpp"
 #include "smx_block.hpp"
 #include "smx_sweep.hpp"
@@ -1522,6 +1526,66 @@ int smx_host_cols(const double* T, int64_t ld, int32_t n, int32_t m, const int32
         (int64_t)n + m + K > INT32_MAX)
         return -1;
     host_cols(T, ld, n, m, basis, nonbasis, A, K, W_out, ld_out, basis_out, nonbasis_out);
+    return 0;
+}
+
+// ---- branch and bound: the pick on solved nodes and the children's tables (smx_branch.hpp) -----
+// The envelope is smx_batch_cuts_fits: a child is an extended table; neither kernel holds LDS.
+int smx_batch_branch_fits(int32_t Rmax_out, int32_t ldb) {
+    return smx_batch_cuts_fits(Rmax_out, ldb);
+}
+
+int smx_batch_branch_pick(const double* final, const int32_t* dims, int32_t Q, int32_t Rmax,
+                          int32_t ldb, const int32_t* basis, const int32_t* ints, int32_t B,
+                          const int32_t* lp, double tol, int32_t* bvar, int32_t* brow,
+                          double* bval, double* bneg, double* bmin, void* stream) {
+    if (Q < 0 || B < 0 || sol_lds_bytes(Rmax, ldb) < 0) return (int)hipErrorInvalidValue;
+    if (Q == 0) return 0;
+    if (!final || !dims || !basis || (!ints && B > 0) || !lp || !bvar || !brow || !bval ||
+        !bneg || !bmin)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_batch_branch_pick, dim3((unsigned)((Q + kBrnWaves - 1) / kBrnWaves)),
+                       dim3(kBrnBlock), 0, S(stream), final, dims, Q, Rmax, ldb, basis, ints, B, lp,
+                       tol, bvar, brow, bval, bneg, bmin);
+    return (int)hipGetLastError();
+}
+
+int smx_batch_branch(const double* final, const int32_t* dims, int32_t Q, int32_t Rmax,
+                     int32_t ldb, const int32_t* basis, const int32_t* nonbasis,
+                     const double* func, const int32_t* src, const int32_t* brow, int32_t Qc,
+                     int32_t Rmax_out, double snap, double* tabs_c, int32_t* dims_c,
+                     int32_t* basis_c, int32_t* nonbasis_c, double* func_c, void* stream) {
+    if (Q < 0 || Qc < 0 || Qc > INT32_MAX / 2 || Rmax_out < Rmax || sol_lds_bytes(Rmax, ldb) < 0 ||
+        sol_lds_bytes(Rmax_out, ldb) < 0)
+        return (int)hipErrorInvalidValue;
+    if (Qc == 0) return 0;
+    if ((Q > 0 && (!final || !dims || !basis || !nonbasis || !func || !brow)) || !src ||
+        !tabs_c || !dims_c || !basis_c || !nonbasis_c || !func_c)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_batch_branch, dim3((unsigned)Qc), dim3(kBrnBlock), 0, S(stream), final,
+                       dims, Q, Rmax, ldb, basis, nonbasis, func, src, brow, Qc, Rmax_out, snap,
+                       tabs_c, dims_c, basis_c, nonbasis_c, func_c);
+    return (int)hipGetLastError();
+}
+
+int smx_host_branch_pick(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                         const int32_t* ints, double tol, int32_t* bvar, int32_t* brow,
+                         double* bval, double* bneg, double* bmin) {
+    if (!T || !basis || !ints || !bvar || !brow || !bval || !bneg || !bmin || n < 1 || m < 1 ||
+        ld < (int64_t)m + 1 || (int64_t)n + m > INT32_MAX)
+        return -1;
+    host_branch_pick(T, ld, n, m, basis, ints, tol, bvar, brow, bval, bneg, bmin);
+    return 0;
+}
+
+int smx_host_branch(const double* T, int64_t ld, int32_t n, int32_t m, const int32_t* basis,
+                    const int32_t* nonbasis, int32_t p, double snap, double* E_down,
+                    double* E_up, int64_t ld_out, int32_t* basis_out) {
+    if (!T || !basis || !nonbasis || !E_down || !E_up || !basis_out || n < 1 || m < 1 ||
+        ld < (int64_t)m + 1 || ld_out < (int64_t)m + 1 || (int64_t)n + m + 1 > INT32_MAX ||
+        p < 0 || p >= n || basis[p] < 0 || basis[p] >= m)
+        return -1;
+    host_branch(T, ld, n, m, basis, nonbasis, p, snap, E_down, E_up, ld_out, basis_out);
     return 0;
 }
 

@@ -10,7 +10,8 @@ from . import _lib
 _lib.load()  # no silent fallback: a missing/broken libsmx.so is an import error
 
 from .engine import Error, Info, Ranging, Scenario, SimplexMethod, Solution  # noqa: E402
+from .branch import IntegerSolution  # noqa: E402
 from .device import DeviceTableau  # noqa: E402
 
-__all__ = ["SimplexMethod", "Info", "Error", "Solution", "Ranging", "Scenario",
+__all__ = ["SimplexMethod", "Info", "Error", "Solution", "Ranging", "Scenario", "IntegerSolution",
            "DeviceTableau"]

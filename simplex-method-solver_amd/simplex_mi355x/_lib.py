@@ -124,6 +124,8 @@ EXPORTS = (
     "smx_batch_scenario", "smx_batch_scenario_fits", "smx_host_scenario", "smx_batch_solution_from",
     "smx_batch_cuts", "smx_batch_cuts_fits", "smx_host_cuts",
     "smx_batch_cols", "smx_batch_cols_fits", "smx_host_cols",
+    "smx_batch_branch_pick", "smx_batch_branch", "smx_batch_branch_fits",
+    "smx_host_branch_pick", "smx_host_branch",
     "smx_comm_unique_id", "smx_comm_init", "smx_comm_destroy",
     "smx_shard_run", "smx_shard_run_timed", "smx_shard_pack", "smx_shard_merge", "smx_shard_update", "smx_shard_begin",
     "smx_shard_finish", "smx_shard_fused_prime", "smx_shard_fused_begin",
@@ -226,6 +228,15 @@ def load():
                             vp, vp, vp], ctypes.c_int),
         "smx_batch_cols_fits": ([i32, i32], ctypes.c_int),
         "smx_host_cols": ([vp, i64, i32, i32, vp, vp, vp, i32, vp, i64, vp, vp], ctypes.c_int),
+        "smx_batch_branch_pick": ([vp, vp, i32, i32, i32, vp, vp, i32, vp, ctypes.c_double, vp, vp,
+                                   vp, vp, vp, vp], ctypes.c_int),
+        "smx_batch_branch": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32,
+                              ctypes.c_double, vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        "smx_batch_branch_fits": ([i32, i32], ctypes.c_int),
+        "smx_host_branch_pick": ([vp, i64, i32, i32, vp, vp, ctypes.c_double, vp, vp, vp, vp, vp],
+                                 ctypes.c_int),
+        "smx_host_branch": ([vp, i64, i32, i32, vp, vp, i32, ctypes.c_double, vp, vp, i64, vp],
+                            ctypes.c_int),
         "smx_shard_begin": ([vp, sp, i32, vp, vp, vp, vp], ctypes.c_int),
         "smx_shard_finish": ([vp, vp, vp, i32, sp, i32, vp, vp, i64, vp, vp, vp], ctypes.c_int),
         "smx_shard_fused_prime": ([vp, sp, i32, vp, vp, vp], ctypes.c_int),

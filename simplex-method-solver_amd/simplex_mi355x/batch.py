@@ -48,6 +48,14 @@ under its LP's final basis, and the solve kernel that takes the widened block ca
 there.  A new variable leaves the constants alone, so after an optimum the widened
 table is primal feasible and the default rule is an ordinary primal simplex from it.
 
+``solve_batch_integer`` (and ``solve_batch_integer_arrays``) answer "these variables must be whole
+numbers" by branch and bound, level by level, the tables never leaving the device:
+``k_batch_branch_pick`` (csrc/smx_branch.hpp) finds the variable to branch on in every solved
+node, the host keeps incumbents and lists the nodes to expand (``branch.Tree``, shared with
+``SimplexMethod.solve_integer``), ``k_batch_branch`` writes both children of each -- a bound row
+under the parent's final basis -- and one warm solve under the dual rule re-solves them all; a
+child is a node, so the chain goes on.
+
 The host side of all this is stated once.  Array level: ``_launch_arrays`` and
 ``_launch_tier`` check a launch, ``_device_solve`` / ``_device_solution`` / ``_device_ranging``
 enqueue one kernel each on fresh outputs, ``_enqueue_base`` and ``_base_arrays`` are
@@ -1229,6 +1237,227 @@ def solve_batch_columns(problems, columns, max_pivots: int = 256, warm_pivots=No
             raise ValueError("a new variable must hold one coefficient per constraint and a cost")
     return _solve_batch_grown(True, problems, columns, max_pivots, warm_pivots, cold_fallback,
                               device, kernel, warm_rule)
+
+
+def branch_fits(Rmax_out: int, ldb: int) -> bool:
+    """Whether blocks of Rmax_out x ldb are inside the branch kernels' envelope (``cuts_fits``)."""
+    return bool(_envelope("smx_batch_branch_fits", Rmax_out, ldb, False))
+
+
+def _device_pick(L, stream, node, d_ints, d_lp, tol):
+    """Enqueue smx_batch_branch_pick on the nodes ``node`` = (final, dims, basis, nonbasis, func)
+    on fresh outputs; returns the device tensors (bvar, brow, bval, bneg, bmin)."""
+    d_final, d_dims, d_basis = node[0], node[1], node[2]
+    Q, Rmax, ldb = d_final.shape
+    dev = d_final.device
+    d_bvar = torch.empty(Q, dtype=torch.int32, device=dev)
+    d_brow = torch.empty(Q, dtype=torch.int32, device=dev)
+    d_bval, d_bneg, d_bmin = (torch.empty(Q, dtype=torch.float64, device=dev) for _ in "vnm")
+    _lib.check(L.smx_batch_branch_pick(
+        d_final.data_ptr(), d_dims.data_ptr(), Q, Rmax, ldb, d_basis.data_ptr(),
+        d_ints.data_ptr(), d_ints.shape[0], d_lp.data_ptr(), float(tol), d_bvar.data_ptr(),
+        d_brow.data_ptr(), d_bval.data_ptr(), d_bneg.data_ptr(), d_bmin.data_ptr(),
+        stream.cuda_stream), "smx_batch_branch_pick")
+    return d_bvar, d_brow, d_bval, d_bneg, d_bmin
+
+
+def _device_branch(L, stream, node, d_src, d_brow, Rout, snap):
+    """Enqueue smx_batch_branch for the parents ``d_src`` of the nodes ``node`` on fresh outputs
+    of ``Rout`` rows; returns the children as (tabs, dims, basis, nonbasis, func)."""
+    d_final, d_dims, d_basis, d_nonbasis, d_func = node
+    Q, Rmax, ldb = d_final.shape
+    Qc, dev = len(d_src), d_final.device
+    d_tc = torch.empty((2 * Qc, Rout, ldb), dtype=torch.float64, device=dev)
+    d_dc = torch.empty((2 * Qc, 3), dtype=torch.int32, device=dev)
+    d_bc = torch.empty((2 * Qc, Rout), dtype=torch.int32, device=dev)
+    d_nc = torch.empty((2 * Qc, ldb), dtype=torch.int32, device=dev)
+    d_fc = torch.empty((2 * Qc, ldb), dtype=torch.float64, device=dev)
+    _lib.check(L.smx_batch_branch(
+        d_final.data_ptr(), d_dims.data_ptr(), Q, Rmax, ldb, d_basis.data_ptr(),
+        d_nonbasis.data_ptr(), d_func.data_ptr(), d_src.data_ptr(), d_brow.data_ptr(), Qc, Rout,
+        float(snap), d_tc.data_ptr(), d_dc.data_ptr(), d_bc.data_ptr(), d_nc.data_ptr(), d_fc.data_ptr(),
+        stream.cuda_stream), "smx_batch_branch")
+    return d_tc, d_dc, d_bc, d_nc, d_fc
+
+
+def solve_batch_integer_arrays(tabs: np.ndarray, dims: np.ndarray, integers=None,
+                               max_pivots: int = 256, warm_pivots=None, max_depth: int = 16,
+                               max_nodes=None, int_tol: float = 1e-6, rule: str = "reference",
+                               kernel: str = "auto", device=None) -> dict:
+    """Array-level integer solve: every LP of ``tabs`` / ``dims`` (as in ``solve_batch_arrays``)
+    with the variables marked in ``integers`` (None: all; else [B][ldb - 1], non-zero: x{k+1} of
+    problem k must be whole) held to whole numbers, by branch and bound on the device.  The
+    method minimises ``function . x``.
+
+    The root solve is ``solve_batch_arrays``'s chain under ``rule``; only roots at SMX_OPTIMUM
+    enter the tree.  Then level by level, the tables never leaving the device: the pick on the
+    frontier (``smx_batch_branch_pick``); ``status``, ``objective`` and the pick's per-node
+    scalars come back (small arrays only) and the host updates every problem's incumbent (an integral node, the
+    lowest objective), prunes (a node whose objective is not below its problem's incumbent) and
+    lists the nodes to expand; ``smx_batch_branch`` writes both children of each into fresh
+    buffers (the parents' are released once the children are solved: two frontiers are alive);
+    one warm solve of all children under SMX_RULE_DUAL capped at ``warm_pivots`` (default:
+    ``max_pivots``) on the kernel chosen once by ``warm_kernel(base, Rmax + max_depth, ldb)``;
+    ``smx_batch_solution_from(group=1)`` with the children's own labels.  From level 1 on every
+    block has Rmax + max_depth rows.  A child at SMX_INCORRECT on a row that misses by more than
+    ``int_tol`` is empty and dropped (``branch.Tree.children``: the pick also reports how far a
+    node's constants are below zero, since the kernels compare with zero exactly; a constant that
+    misses zero from below by less is written to the children as zero).  A node that
+    can be neither closed nor expanded -- a warm run at its cap or at SMX_NOT_CONVERGE, a node at
+    ``max_depth``, what a frontier past ``max_nodes`` children (default: what keeps two frontiers
+    under ``GM_TABLE_BUDGET``; the lowest objectives are kept, ties by node index) leaves out --
+    counts a valid lower bound into its problem's ``bound`` and makes its status ``"limit"``:
+    ``"optimal"`` is reported only when every node of the problem was closed.  A shape whose
+    blocks of Rmax + max_depth rows leave every tier raises ValueError before anything is
+    enqueued.  ``int_tol``: how far from a whole number a marked variable may stand and count as
+    whole; 1e-6 is a convention of LP-based integer solvers, not a measured number.
+
+    Returns per problem: ``status`` (list of "optimal", "infeasible", "limit" or the root's own
+    "error" / "cap"), ``x`` [B][ldb - 1] (the marked variables rounded to the nearest whole number;
+    NaN without an answer), ``x_raw``, ``objective`` [B] (on the rounded ``x``, by
+    ``smx_batch_solution``'s ordered sum; +inf without an answer), ``bound`` [B], ``nodes``,
+    ``warm_pivots`` and ``depth`` [B], ``found`` [B] (whether ``x`` holds an answer) and
+    ``root_status`` (SMX_* codes)."""
+    from . import branch
+    _kernel_name(kernel)
+    code = _lib.rule_code(rule)
+    tabs, dims, (B, Rmax, ldb) = _launch_arrays(tabs, dims)
+    if integers is None:
+        integers = np.ones((B, ldb - 1), dtype=np.int32)
+    integers = np.asarray(integers)
+    if integers.shape != (B, ldb - 1):
+        raise ValueError("integers must be [B][ldb - 1]")
+    depth = int(max_depth)
+    if depth < 0:
+        raise ValueError("max_depth must not be negative")
+    _need_device()
+    Rout = Rmax + depth
+    which = _launch_tier(dims, (B, Rmax, ldb), kernel)
+    warm = warm_kernel(which, Rout, ldb) if B else "wave"
+    if solution_lds_bytes(Rout, ldb) < 0 or not branch_fits(Rout, ldb):
+        raise ValueError(ENVELOPE_ERROR)
+    P = int(max_pivots)
+    Pw = P if warm_pivots is None else int(warm_pivots)
+    if max_nodes is None:
+        max_nodes = branch.default_max_nodes(Rout, ldb, GM_TABLE_BUDGET)
+    h_ints = np.zeros((B, ldb), dtype=np.int32)
+    h_ints[:, :ldb - 1] = integers != 0
+    tree = branch.Tree(B, depth, max_nodes, int_tol)
+    L = _lib.load()
+    dev = torch.device(device if device is not None else "cuda")
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        d_tabs = torch.from_numpy(tabs).to(dev)
+        d_dims = torch.from_numpy(dims).to(dev)
+        d_ints = torch.from_numpy(h_ints).to(dev)
+        run, d_func, sol, _ = _enqueue_base(L, stream, which, d_tabs, d_dims, P, rule=code)
+        root_status = run[3].cpu().numpy()
+        root_np = run[4].cpu().numpy()
+        live = tree.start([_status_name(int(s), int(p), P) for s, p in zip(root_status, root_np)])
+        h_obj = sol[2].cpu().numpy()
+        frontier = [(k, k, float(h_obj[k])) for k in live]
+        node, d_x = (run[0], d_dims, sol[3], sol[4], d_func), sol[0]
+        h_lp = np.arange(B, dtype=np.int32)
+        level = 0
+        picks = _device_pick(L, stream, node, d_ints, torch.from_numpy(h_lp).to(dev), int_tol)
+        while frontier:
+            d_brow = picks[1]
+            parents = tree.close(
+                level, frontier, picks[0].cpu().numpy(),
+                lambda qs: d_x[torch.as_tensor(qs, dtype=torch.long, device=dev)].cpu().numpy())
+            if not parents:
+                break
+            level += 1
+            h_src = np.array([q for q, _, _ in parents], dtype=np.int32)
+            d_src = torch.from_numpy(h_src).to(dev)
+            kids = _device_branch(L, stream, node, d_src, d_brow, Rout, int_tol)
+            d_out, d_rc, _, d_st, d_np, _ = _device_solve(L, stream, warm, kids[0], kids[1], Pw,
+                                                          rule=_lib.RULE_DUAL)
+            wsol = _device_solution(L, stream, d_out, kids[1], Pw, d_rc, d_np, kids[4],
+                                    (kids[2], kids[3], 1))
+            h_lp = np.repeat(h_lp[h_src], 2)
+            node, d_x = (d_out, kids[1], wsol[3], wsol[4], kids[4]), wsol[0]
+            picks = _device_pick(L, stream, node, d_ints, torch.from_numpy(h_lp).to(dev), int_tol)
+            frontier = tree.children(level, parents, d_st.cpu().numpy(), d_np.cpu().numpy(),
+                                     wsol[2].cpu().numpy(), picks[3].cpu().numpy(),
+                                     picks[4].cpu().numpy())
+            del kids, d_rc                                   # the parents' buffers go with `node`
+    res = {"status": [], "x": np.full((B, ldb - 1), np.nan), "x_raw": np.full((B, ldb - 1), np.nan),
+           "objective": np.full(B, np.inf), "bound": np.zeros(B),
+           "nodes": np.zeros(B, dtype=np.int64), "warm_pivots": np.zeros(B, dtype=np.int64),
+           "depth": np.zeros(B, dtype=np.int64), "root_status": root_status,
+           "found": np.zeros(B, dtype=bool)}
+    for k in range(B):
+        n, m = int(dims[k, 0]), int(dims[k, 1])
+        ans = tree.answer(k, tabs[k, n, :m], h_ints[k, :m])
+        res["status"].append(ans.status)
+        if ans.x is not None:
+            res["found"][k] = True
+            res["x"][k, :m], res["x_raw"][k, :m] = ans.x, ans.x_raw
+            res["x"][k, m:] = res["x_raw"][k, m:] = 0.0
+        res["objective"][k], res["bound"][k] = ans.objective, ans.bound
+        res["nodes"][k], res["warm_pivots"][k], res["depth"][k] = (ans.nodes, ans.warm_pivots,
+                                                                   ans.depth)
+    return res
+
+
+def solve_batch_integer(problems, integers=None, max_pivots: int = 256, warm_pivots=None,
+                        max_depth: int = 16, max_nodes=None, int_tol: float = 1e-6,
+                        rule: str = "reference", kernel: str = "auto", device=None):
+    """Solve every ``(constraints, function)`` with the variables marked in ``integers[k]`` (None,
+    for the call or for a problem: all of them; else m truth values) held to whole numbers;
+    returns one ``IntegerSolution`` (branch.py) per problem, or the ``IndexError`` the reference
+    would raise.  The method minimises ``function . x``.
+
+    Routing and launch grouping are ``solve_batch_cuts``'s.  Problems routed ``"single"``, and
+    those of a launch whose blocks of Rmax + max_depth rows leave every batch kernel's envelope, go
+    through ``SimplexMethod.solve_integer`` one by one; every other launch runs its trees on the
+    device (``solve_batch_integer_arrays``), where ``max_nodes`` caps a launch's frontier.  Both
+    walk the same tree by the same rules (``branch.Tree``)."""
+    from .branch import IntegerSolution, mask_of
+    problems = list(problems)
+    _kernel_name(kernel)
+    _lib.rule_code(rule)
+    if integers is None:
+        integers = [None] * len(problems)
+    integers = list(integers)
+    if len(integers) != len(problems):
+        raise ValueError("integers must hold one entry per problem")
+    P = int(max_pivots)
+    Pw = P if warm_pivots is None else int(warm_pivots)
+    results = [None] * len(problems)
+
+    def single(k, c, f):
+        try:
+            results[k] = SimplexMethod(c, f).solve_integer(integers[k], P, Pw, max_depth,
+                                                           max_nodes, int_tol, rule)
+        except IndexError as exc:    # where the reference itself raises (simplex.py:49, 95, 159)
+            results[k] = exc
+
+    def launch(which, idx, tabs, dims):
+        _, Rmax, ldb = tabs.shape
+        try:
+            warm_kernel(which, Rmax + int(max_depth), ldb)
+        except ValueError:
+            for k in idx:
+                single(k, *problems[k])
+            return
+        mask = np.zeros((len(idx), ldb - 1), dtype=np.int32)
+        for q, k in enumerate(idx):
+            mask[q, :int(dims[q, 1])] = mask_of(integers[k], int(dims[q, 1]))
+        out = solve_batch_integer_arrays(tabs, dims, mask, P, Pw, max_depth, max_nodes, int_tol,
+                                         rule, which, device)
+        for q, k in enumerate(idx):
+            m = int(dims[q, 1])
+            has = bool(out["found"][q])
+            results[k] = IntegerSolution(
+                out["status"][q], out["x"][q, :m].copy() if has else None,
+                out["x_raw"][q, :m].copy() if has else None, float(out["objective"][q]),
+                float(out["bound"][q]), int(out["nodes"][q]), int(out["warm_pivots"][q]),
+                int(out["depth"][q]))
+
+    _drive(problems, kernel, max_pivots, False, single, launch)
+    return results
 
 
 def _table(T, n, flen, m):

@@ -14,6 +14,7 @@ Additions (not in the reference, all opt-in): ``step()`` (one pick + pivot), ``s
 (``get_solution`` with an optional pivot cap, or the chained no-history fast path),
 ``solution()`` (every variable, the duals and the objective of the current table),
 ``ranging()`` (how far each constant and each cost can move before the basis changes),
+``solve_integer()`` (branch and bound with marked variables held to whole numbers),
 ``pivots`` / ``pivot_log`` and ``status``.
 
 Deliberate differences, all on inputs the reference UI never produces (main.py:309-312 always
@@ -638,6 +639,94 @@ class SimplexMethod:
                     + list(self.function[m:]))
         return self._successor(W, n, function, row, list(self.column), 1 + max(n, m + K),
                                m=m + K, flen=self.flen + K)
+
+    def _branch_pick(self, mask, tol):
+        """(bvar, brow, bval, bneg, bmin) of the current table under the mask ``mask`` [m] (int32):
+        ``smx_host_branch_pick`` (include/smx.h) on the backend's ``download()``."""
+        import ctypes
+        basis, _ = self._label_codes()
+        T = self._dense_table()
+        bvar, brow = ctypes.c_int32(), ctypes.c_int32()
+        bval, bneg, bmin = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        err = _lib.load().smx_host_branch_pick(
+            T.ctypes.data, T.shape[1], self.n, self.m, basis.ctypes.data, mask.ctypes.data,
+            float(tol), ctypes.byref(bvar), ctypes.byref(brow), ctypes.byref(bval),
+            ctypes.byref(bneg), ctypes.byref(bmin))
+        if err:
+            raise RuntimeError(f"smx_host_branch_pick refused n={self.n}, m={self.m} ({err})")
+        return bvar.value, brow.value, bval.value, bneg.value, bmin.value
+
+    def _branch(self, p, snap=0.0):
+        """The down and the up child of the current table branched on row ``p``
+        (``smx_host_branch``, include/smx.h; ``snap`` is its tolerance), each a new object on this one's backend with one
+        more constraint row 'y{n+1}', as ``add_constraints`` would leave it."""
+        n, m = self.n, self.m
+        basis, nonbasis = self._label_codes()
+        T = self._dense_table()
+        E = [np.empty((n + 2, m + 1), dtype=np.float64) for _ in range(2)]
+        basis_out = np.empty(n + 1, dtype=np.int32)
+        err = _lib.load().smx_host_branch(
+            T.ctypes.data, T.shape[1], n, m, basis.ctypes.data, nonbasis.ctypes.data, int(p),
+            float(snap), E[0].ctypes.data, E[1].ctypes.data, m + 1, basis_out.ctypes.data)
+        if err:
+            raise RuntimeError(f"smx_host_branch refused n={n}, m={m}, row {p} ({err})")
+        column = list(self.column[:n]) + ['y' + str(n + 1)] + list(self.column[n:])
+        return [self._successor(e, n + 1, list(self.function), list(self.row), list(column),
+                                1 + max(n + 1, m)) for e in E]
+
+    def solve_integer(self, integers=None, max_pivots=None, warm_pivots=None, max_depth=16,
+                      max_nodes=None, int_tol=1e-6, rule="reference"):
+        """Solve the problem with the variables marked in ``integers`` (None: all of them; else m
+        truth values) held to whole numbers, by branch and bound; returns an
+        ``IntegerSolution`` (branch.py).  The method minimises ``function . x``.
+
+        The root is ``solve(record_history=False, max_pivots=max_pivots, rule=rule)`` on this
+        object; only a root at ``"optimum"`` enters the tree, any other status is passed through.
+        The tree is walked level by level with the rules of ``branch.Tree``, the same walk as
+        ``batch.solve_batch_integer_arrays``: the pick is ``smx_host_branch_pick``, the children
+        are ``smx_host_branch``'s tables (include/smx.h) as new objects on this one's backend, and
+        each is solved by ``solve(rule="dual")`` capped at ``warm_pivots`` (default:
+        ``max_pivots``) -- on every backend, so on the device and sharded backends this is
+        correct, not fast.  A child that ends at "incorrect system" on a row that misses by more
+        than ``int_tol`` is empty (``Tree.children``; a constant that misses zero from below by
+        less is written to the children as zero); one that ends anywhere else but an optimum,
+        a node at ``max_depth`` and what a frontier past ``max_nodes`` children leaves out stay
+        open and make the status ``"limit"``.
+        ``int_tol`` is how far from a whole number a marked variable may stand and count as whole:
+        1e-6 is a convention of LP-based integer solvers, not a measured number."""
+        from . import branch
+        _lib.rule_code(rule)
+        mask = branch.mask_of(integers, self.m)
+        Pw = max_pivots if warm_pivots is None else warm_pivots
+        if max_nodes is None:
+            max_nodes = branch.default_max_nodes(self.n + 1 + int(max_depth), self.m + 1)
+        tree = branch.Tree(1, max_depth, max_nodes, int_tol)
+        self.solve(record_history=False, max_pivots=max_pivots, rule=rule)
+        function = list(self.function)
+        frontier, nodes, level = [], [self], 0
+        if tree.start([self.status]):
+            frontier = [(0, 0, self.solution().objective)]
+        codes = {"optimum": _lib.OPTIMUM, "cap": _lib.PIVOT}
+        codes.update({text: code for code, text in MESSAGES.items()})
+        picks = [self._branch_pick(mask, int_tol)] if frontier else []
+        while frontier:
+            parents = tree.close(level, frontier, [v[0] for v in picks],
+                                 lambda qs: [nodes[q].solution().x for q in qs])
+            if not parents:
+                break
+            level += 1
+            kids, status = [], []
+            for q, _, _ in parents:
+                for child in nodes[q]._branch(picks[q][1], int_tol):
+                    out = child.solve(record_history=False, max_pivots=Pw, rule="dual")
+                    kids.append(child)
+                    status.append(codes[str(out[-1]) if child.status == "error" else child.status])
+            nodes = kids
+            picks = [c._branch_pick(mask, int_tol) for c in kids]
+            frontier = tree.children(level, parents, status, [c.pivots for c in kids],
+                                     [c.solution().objective for c in kids],
+                                     [v[3] for v in picks], [v[4] for v in picks])
+        return tree.answer(0, function, mask)
 
     # ---------------------------------------------------------------- the hot path -------
     def _rule_twin(self):
